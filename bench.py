@@ -24,6 +24,9 @@ packs through the host): the configuration of tests/test_gpu_multirank_one_gpu.p
 `--forward-only` is the animation leg (configs[4]): a step = one FRAME per rank (re-anchor on the posed mesh + no-grad render,
 frame k on rank k mod N; N > 1: one image all-gather per step, in flight under the next frame's render); value = P * frames / t.
 
+`--dump-outputs DIR` writes what the last of the K timed steps handed its caller (images, radii, gradients; the last frame
+with --forward-only) as DIR/<name>.npy (`dump_outputs`); the inputs are seeded, so two builds compare output for output.
+
 Extra objects on the JSON line:
   roofline      dominant kernel, timed live with HIP events recorded by the library on its launch stream
   cpu_baseline  the PyTorch CPU oracle, full fwd+bwd of the same view on the host cores (rank 0, N=1)
@@ -87,6 +90,24 @@ def algorithmic_bytes(stage, P, M, R, npix, T, B=1):
     }[stage]
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs: data bytes of all arrays together
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every tensor of `outputs` as <path>/<name>.npy in float32 (radii are small integers: exact).
+    Above DUMP_BYTES in all, every array keeps the same share of its elements at fixed, seeded, sorted flat positions
+    (the positions depend on the array's size only: two builds sample the same elements)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_spawn(args):
     """`python bench.py --gpus N` with no launcher: become the launcher the driver would use."""
     with socket.socket() as s:
@@ -133,6 +154,10 @@ def main():
     ap.add_argument("--forward-only", action="store_true",
                     help="the animation leg (configs[4]): a step = one frame per rank - re-anchor on the posed mesh + no-grad render - "
                          "frames sharded over the ranks, + one image all-gather per step for N > 1; reports frames/s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the LAST timed step handed its caller (images, radii, gradients; "
+                         "rank 0) as DIR/<name>.npy in float32, at most 64 MB in all (above that, a fixed seeded sample of "
+                         "every array): the same arguments give the same inputs, so two builds compare output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -230,17 +255,22 @@ def main():
             self.gd = (torch.randn(shp + (1, RES, RES), generator=g) * 1e-3).to(dev)
             self.ga = (torch.randn(shp + (1, RES, RES), generator=g) * 1e-3).to(dev)
 
-        def step(self):
+        def step(self, capture=False):
+            """capture: keep what the caller receives (forward outputs, then the gradients) in self.outputs"""
             L = self.leaves
             if self.forward_only:
                 with torch.no_grad():
                     if self.views > 1:
-                        return rasterize_gaussians_batch(L["means3D"], None, L["shs"], None, L["opacities"],
-                                                         L["scales"], L["rotations"], None, self.rs)[0]
-                    return self.rast(means3D=L["means3D"], means2D=L["means3D"], shs=L["shs"], opacities=L["opacities"],
-                                     scales=L["scales"], rotations=L["rotations"])[0]
+                        out = rasterize_gaussians_batch(L["means3D"], None, L["shs"], None, L["opacities"],
+                                                        L["scales"], L["rotations"], None, self.rs)
+                    else:
+                        out = self.rast(means3D=L["means3D"], means2D=L["means3D"], shs=L["shs"], opacities=L["opacities"],
+                                        scales=L["scales"], rotations=L["rotations"])
+                if capture:
+                    self.outputs = dict(zip(("color", "radii", "depth", "alpha"), out))
+                return out[0]
             if self.seq_views > 1 or (world > 1 and self.views == 1):
-                return self.step_rounds()
+                return self.step_rounds(capture)
             for t in L.values():
                 t.grad = None
             # the zero-filled leaf the reference's render() creates per view (gaussian_renderer/__init__.py:26), built the way
@@ -262,12 +292,22 @@ def main():
                 with _rast.packed_gradients() as pg:
                     torch.autograd.grad([color, depth, alpha], [L[k] for k in PARAMS] + [means2D], [self.gc, self.gd, self.ga])
                     pack = pg.take()
-                return vp.allgather_reduce_unpacked(pack, self.shapes, mode=collective_mode[0])
+                res = vp.allgather_reduce_unpacked(pack, self.shapes, mode=collective_mode[0])
+                if capture:
+                    self.capture_outputs(color, radii, depth, alpha, res[0])
+                return res
             torch.autograd.backward([color, depth, alpha], [self.gc, self.gd, self.ga])
+            if capture:
+                self.capture_outputs(color, radii, depth, alpha, {k: L[k].grad for k in PARAMS} | {"means2D": means2D.grad})
             return means2D.grad
 
-        def step_rounds(self):
-            """The reference's loop over the rank's views; N > 1: one all-gather per round, in flight under the next round."""
+        def capture_outputs(self, color, radii, depth, alpha, grads):
+            self.outputs = {"color": color, "radii": radii, "depth": depth, "alpha": alpha}
+            self.outputs.update({"grad_" + k: g for k, g in grads.items()})
+
+        def step_rounds(self, capture=False):
+            """The reference's loop over the rank's views; N > 1: one all-gather per round, in flight under the next round.
+            capture: the last round's forward outputs and the step's gradients (N > 1: reduced over the ranks)."""
             L = self.leaves
             total, pending = None, None
             for j in range(self.seq_views):
@@ -282,7 +322,10 @@ def main():
                         torch.autograd.grad([color, depth, alpha], [L[k] for k in PARAMS] + [means2D], [self.gc, self.gd, self.ga])
                         pack = pg.take()
                     if self.seq_views == 1:
-                        return vp.allgather_reduce_unpacked(pack, self.shapes, mode=collective_mode[0])
+                        res = vp.allgather_reduce_unpacked(pack, self.shapes, mode=collective_mode[0])
+                        if capture:
+                            self.capture_outputs(color, radii, depth, alpha, res[0])
+                        return res
                     started = vp.PackGather(pack, async_op=True)
                     if pending is not None:
                         total = vp.reduce_gathered(pending.result(), total)
@@ -290,10 +333,16 @@ def main():
                 else:
                     torch.autograd.backward([color, depth, alpha], [self.gc, self.gd, self.ga])
             if pending is not None:
-                return vp.reduce_gathered_unpacked(pending.result(), total, self.shapes)
+                res = vp.reduce_gathered_unpacked(pending.result(), total, self.shapes)
+                if capture:
+                    self.capture_outputs(color, radii, depth, alpha, res[0])
+                return res
+            if capture:
+                self.capture_outputs(color, radii, depth, alpha, {k: L[k].grad for k in PARAMS} | {"means2D": means2D.grad})
             return means2D.grad
 
-        def timed(self, steps, warmup, init_steps=None):
+        def timed(self, steps, warmup, init_steps=None, capture=False):
+            """capture: the last timed step keeps its outputs in self.outputs (--dump-outputs)"""
             init_steps = args.init_steps if init_steps is None else init_steps
             # first-use initialisation, not part of W: the rasterizer's decaying capacity / longest-list
             # estimates settle over the first calls (retries, buffer growth), the GPU leaves its idle clocks
@@ -302,8 +351,10 @@ def main():
                 self.step()
             fence()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 self.step()
+            if steps > 0:
+                self.step(capture=capture)
             fence()
             elapsed = time.perf_counter() - t0
             if world > 1:
@@ -420,18 +471,20 @@ def main():
         def frame(self, i):
             return self.anim.render_frame(self.verts[i % self.num_poses], self.cams[i % 360])
 
-        def run(self, rounds, first=0):
+        def run(self, rounds, first=0, capture=False):
             n = 0
-            for _ in self.an.render_frames_parallel(range(first, first + rounds * world), self.frame, gather=self.gather):
+            for frame in self.an.render_frames_parallel(range(first, first + rounds * world), self.frame, gather=self.gather):
                 n += 1
+            if capture and n:
+                self.outputs = {"image": frame[1]}          # the last frame this rank received
             return n
 
-        def timed(self, steps, warmup, init_steps=None):
+        def timed(self, steps, warmup, init_steps=None, capture=False):
             init_phase(lambda: self.run(1), args.init_steps if init_steps is None else init_steps)
             self.run(warmup)
             fence()
             t0 = time.perf_counter()
-            self.run(steps, first=7)
+            self.run(steps, first=7, capture=capture)
             fence()
             elapsed = time.perf_counter() - t0
             if world > 1:
@@ -442,7 +495,9 @@ def main():
     if args.forward_only:
         # ---------------- the animation leg (configs[4]): frames/s of re-anchor + forward (+ the image gather for N > 1)
         wl = AnimationWorkload(P, gather=world > 1)
-        elapsed = wl.timed(args.steps, args.warmup)
+        elapsed = wl.timed(args.steps, args.warmup, capture=args.dump_outputs is not None)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, wl.outputs)
         frames = args.steps * world
         line = None
         without = None
@@ -519,7 +574,11 @@ def main():
                               "the reduced shards (same bits, (world-1)/world * 2 packs per rank on the links instead of "
                               "world-1); timed outside the step loop, max over ranks"}
 
-    elapsed = main_wl.timed(args.steps, args.warmup)
+    elapsed = main_wl.timed(args.steps, args.warmup, capture=args.dump_outputs is not None)
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, main_wl.outputs)
+        del main_wl.outputs
     ms = elapsed / args.steps * 1e3
     M = main_wl.M
 

@@ -4,7 +4,8 @@
   amass_test_17_poses.npz   the reference's content/amass_test_17.npz poses (make_motion.py)
 
 Both are third-party data of the reference tree and are NOT redistributed with this repository: the .npz files are
-git-ignored, built locally by the two scripts where /root/reference exists (`__graft_entry__.build()` does it), and every
+git-ignored, built by hand with the two scripts (or `build_if_possible()`) where the reference tree exists - never by
+`__graft_entry__.build()`, so a build's benchmark inputs do not depend on the machine it ran on - and every
 consumer has a procedural fallback (`synth.humanoid_points` / `synth.humanoid_mesh`, `animation.MotionDriver`'s sway) that
 it reports in its workload description.
 """

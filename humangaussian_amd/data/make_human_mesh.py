@@ -1,6 +1,6 @@
 """Generates humangaussian_amd/data/human_mesh.npz - the surface SURVEY.md 8(d) samples its benchmark clouds from.  The
 .npz is a LOCAL, git-ignored artefact (the mesh is a third-party asset of the reference tree: it is not redistributed with
-this repository); `__graft_entry__.build()` runs this script wherever /root/reference exists, the file then travels to the
+this repository); run it by hand where the reference tree exists (`__graft_entry__.build()` does not), the file then travels to the
 GPU box with the working tree like the built .so files.  Without it every consumer falls back to the analytic capsule
 humanoid (`synth.humanoid_points` / `synth.humanoid_mesh`) and says so.
 

@@ -1,6 +1,6 @@
 """Generates humangaussian_amd/data/amass_test_17_poses.npz - the 136 SMPL-X pose frames of the reference's demo motion.
 A LOCAL, git-ignored artefact (the clip is AMASS data, whose licence forbids redistribution: it is not shipped with this
-repository); `__graft_entry__.build()` runs this script wherever /root/reference exists.  Without the file
+repository); run it by hand where the reference tree exists (`__graft_entry__.build()` does not).  Without the file
 `animation.MotionDriver` plays its procedural sway of the same nine joints and period, and says so.  A user's own
 AMASS-format clip (`poses` (F, 55, 3)) can be passed as `MotionDriver(poses_path=...)`.
 

@@ -5,12 +5,11 @@ every input (raw parameters, both Adam moments, the densification statistics, th
 drew, and every output (parameters, moments, statistics after the call).  Run in the build container (imports
 /root/reference, which does not exist on the GPU box):
 
-    python tests/golden/make_densify_fixture.py
+    python tests/golden/make_densify_fixture.py            # (re)write the fixture
+    python tests/golden/make_densify_fixture.py --check    # re-run the reference method, compare with the committed file
 
 tests/test_gpu_bookkeeping.py::test_densify_and_prune_matches_the_reference_method replays the state through
-humangaussian_amd.densify.densify_and_prune on the GPU (masks / row order exact, tensors <= 1e-6);
-tests/test_reference_import_cpu.py::test_densify_fixture_is_what_the_reference_method_produces re-runs this script's
-`run()` where the reference is mounted and compares with the committed file."""
+humangaussian_amd.densify.densify_and_prune on the GPU (masks / row order exact, tensors <= 1e-6)."""
 import os
 import sys
 import types
@@ -113,5 +112,13 @@ def run():
 if __name__ == "__main__":
     res = run()
     path = os.path.join(ROOT, "tests", "golden", "reference_densify.npz")
+    if "--check" in sys.argv:
+        fx = np.load(path)
+        assert sorted(fx.files) == sorted(res)
+        for k in fx.files:
+            assert np.array_equal(fx[k], res[k]), k
+        assert res["out_xyz"].shape[0] != res["in_xyz"].shape[0] and res["samples"].shape[0] > 0
+        print("the committed", path, "is what the reference method produces")
+        sys.exit(0)
     np.savez_compressed(path, **res)
     print("wrote", path, "points", res["in_xyz"].shape[0], "->", res["out_xyz"].shape[0], "split children", res["samples"].shape[0])
