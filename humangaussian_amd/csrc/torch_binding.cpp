@@ -23,6 +23,7 @@
 #include <map>
 #include <tuple>
 #include <mutex>
+#include <utility>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -200,14 +201,19 @@ struct BwdPlan : torch::CustomClassHolder {
   }
 };
 
-// Packed backward (view_parallel.py): while the request is set, a backward whose inputs are the SH / scale / rotation
+// Packed backward (view_parallel.py): while a request is open, a backward whose inputs are the SH / scale / rotation
 // configuration writes ONE (P, 15 + 3M) pack (hgs_backward_batch_packed) - the tensor the rank sends - and hands autograd
-// strided views of it; `take_packed()` collects the pack.  Thread-local: the request belongs to the thread that runs
-// autograd.grad (torch's engine runs a CPU-initiated backward of one device on the calling thread's device worker; the
-// flag is read through a process-wide atomic for that reason, the pack returned per process).
+// strided views of it; `take_packed()` collects the pack.  Process-wide, not thread-local: torch's engine runs a
+// CPU-initiated backward of one device on that device's worker thread, not on the thread that called autograd.grad, so
+// the request is read through an atomic and the pack is kept per process.  Requests nest (an inner exit leaves the outer
+// request open, with its own slot); every rasterizer backward that runs while one is open is counted, and `take_packed()`
+// hands out the pack only when exactly ONE backward ran since the slot was last cleared - a graph with two rasterizer
+// nodes (or one eligible and one not) has no single pack that holds its gradients.
 std::atomic<int> g_pack_request{0};
 std::mutex g_pack_mu;
 Tensor g_last_pack;
+int64_t g_pack_backwards = 0;       // rasterizer backwards since the slot was last cleared (under g_pack_mu)
+std::vector<std::pair<Tensor, int64_t>> g_pack_saved;     // slot + count of each enclosing request (under g_pack_mu)
 
 struct Rasterize : public torch::autograd::Function<Rasterize> {
   // 22 arguments after ctx (backward returns one slot per argument).  `tanfov` is a CPU double
@@ -454,8 +460,13 @@ struct Rasterize : public torch::autograd::Function<Rasterize> {
     // write nothing (NaN gradients) if the slot delivered a stale number (hgs_rast.h: hgs_backward)
     plan->status.num_pairs = (uint32_t)pairs;
     const auto tb1 = std::chrono::steady_clock::now();
-    const bool packed = g_pack_request.load(std::memory_order_relaxed) != 0 && plan->has_sh && plan->has_sr && !plan->has_cp &&
-                        !plan->has_cv && plan->M >= 1 && plan->P > 0;
+    const bool requested = g_pack_request.load(std::memory_order_relaxed) > 0;
+    if (requested) {                          // (eligible or not: `take_packed` needs to know how many nodes there were)
+      std::lock_guard<std::mutex> lk(g_pack_mu);
+      ++g_pack_backwards;
+    }
+    const bool packed = requested && plan->has_sh && plan->has_sr && !plan->has_cp && !plan->has_cv && plan->M >= 1 &&
+                        plan->P > 0;
     if (packed) {
       const int64_t P = plan->P, M = plan->M, F = 15 + 3 * M;
       Tensor pack = at::empty({P, F}, at::TensorOptions().dtype(at::kFloat).device(dev));
@@ -648,19 +659,34 @@ Tensor reduce_view_packs(const Tensor& gathered, const c10::optional<Tensor>& ac
   return out;
 }
 
+// open (on = true) or close one packed-gradients request.  Opening saves the enclosing request's slot and count and
+// starts empty; closing restores them: an inner request neither ends the outer one nor hands its pack to it (a pack the
+// inner request did not take is dropped).
 void set_packed_backward(bool on) {
-  g_pack_request.store(on ? 1 : 0, std::memory_order_relaxed);
-  if (!on) return;
   std::lock_guard<std::mutex> lk(g_pack_mu);
-  g_last_pack = Tensor();
+  if (on) {
+    g_pack_saved.emplace_back(g_last_pack, g_pack_backwards);
+    g_last_pack = Tensor();
+    g_pack_backwards = 0;
+  } else {
+    if (g_pack_saved.empty()) return;               // (unbalanced close: nothing is open)
+    g_last_pack = g_pack_saved.back().first;
+    g_pack_backwards = g_pack_saved.back().second;
+    g_pack_saved.pop_back();
+  }
+  g_pack_request.store((int)g_pack_saved.size(), std::memory_order_relaxed);
 }
 
-// the pack the last packed backward wrote (None if the backward was not eligible: the caller packs the six tensors itself)
+// the pack of the one packed backward since the slot was last cleared, once (None if the backward was not eligible -
+// colours / covariances precomputed -, if none ran, or if more than one rasterizer backward ran: the caller then packs
+// the six tensors itself)
 c10::optional<Tensor> take_packed() {
   std::lock_guard<std::mutex> lk(g_pack_mu);
   Tensor t = g_last_pack;
+  const int64_t n = g_pack_backwards;
   g_last_pack = Tensor();
-  if (!t.defined()) return c10::nullopt;
+  g_pack_backwards = 0;
+  if (!t.defined() || n != 1) return c10::nullopt;
   return t;
 }
 

@@ -148,8 +148,10 @@ class packed_gradients:
     per-Gaussian gradients as ONE (P, 15 + 3M) pack - [means3D 3 | means2D 3, summed over the call's views | sh 3M |
     opacity 1 | scales 3 | rotations 4 | radii 1, max over the views] - straight from its last kernel
     (include/hgs_rast.h: hgs_backward_batch_packed; the tensor the rank all-gathers) and hands autograd strided VIEWS of
-    it; `.take()` returns the pack (None if the backward was not eligible - colours / covariances precomputed, or no
-    backward ran: the caller then packs the six tensors itself)."""
+    it; `.take()` returns the pack, once (None if the backward was not eligible - colours / covariances precomputed -, if
+    no backward ran, or if more than one rasterizer backward ran inside the request: the caller then packs the six
+    tensors itself).  The pack holds the gradients w.r.t. the RASTERIZER's inputs: it is the caller's to know that those
+    are its leaves.  Requests nest: each has its own slot, and an inner exit leaves the outer request open."""
 
     def __enter__(self):
         _lib.load_binding().set_packed_backward(True)

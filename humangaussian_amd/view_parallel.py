@@ -244,10 +244,17 @@ def render_views_parallel(cameras: Sequence, params: Dict[str, torch.Tensor], bg
     outputs = []
 
     # On the HIP path the rasterizer's last backward kernel writes the pack itself (rasterizer.packed_gradients): no
-    # pack kernel, no second pass over the six gradient tensors on the exposed path of a step.
-    hip_pack = dev.type == "cuda"
+    # pack kernel, no second pass over the six gradient tensors on the exposed path of a step.  That pack holds the
+    # gradients w.r.t. the RASTERIZER's inputs, which are the leaves only when the default functions hand the leaves
+    # straight to one rasterizer call; a custom render_fn (activations, re-posed means, a subset, two calls) packs
+    # its autograd result instead.
+    if batched:
+        hip_pack = dev.type == "cuda" and render_batch_fn in (None, hip_render_batch_fn)
+    else:
+        hip_pack = dev.type == "cuda" and render_fn is hip_render_fn
     if hip_pack:
         from .rasterizer import packed_gradients
+    F = 15 + 3 * int(leaves["shs"].shape[1]) if leaves["shs"].dim() == 3 else -1
 
     def grads_of(outs, tens, gouts):
         """-> (gradient tuple, pack or None)"""
@@ -255,7 +262,12 @@ def render_views_parallel(cameras: Sequence, params: Dict[str, torch.Tensor], bg
             return torch.autograd.grad(outs, tens, gouts, allow_unused=True), None
         with packed_gradients() as pg:
             gl = torch.autograd.grad(outs, tens, gouts, allow_unused=True)
-            return gl, pg.take()
+            pack = pg.take()
+        # (a pack that does not fit the leaves - another call's, or none at all - is not used: the caller packs `gl`)
+        if pack is not None and (tuple(pack.shape) != (P, F) or pack.dtype != torch.float32 or not pack.is_contiguous()
+                                 or pack.device != dev):
+            pack = None
+        return gl, pack
 
     def one_view(v, want_pack=False):
         means2D = torch.zeros_like(leaves["means3D"], requires_grad=True)

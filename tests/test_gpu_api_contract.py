@@ -224,7 +224,7 @@ def test_dist_cuda2_grid_search_equals_the_brute_force_bit_for_bit():
     from humangaussian_amd.knn import distCUDA2
     rng = np.random.default_rng(5)
     clouds = {
-        "body_100k": synth.body_points(100_000, seed=0),          # (human.obj where the local asset exists, else the capsule)
+        "body_100k": synth.body_points(100_000, seed=0, source="capsule"),   # (pinned: the same cloud on every machine)
         "gauss": rng.normal(0, 0.4, (20_000, 3)),
         "planar": np.concatenate([rng.uniform(-1, 1, (5000, 2)), np.zeros((5000, 1))], 1),
         "collinear": np.stack([rng.uniform(-3, 3, 3000), np.zeros(3000), np.zeros(3000)], 1),
@@ -233,8 +233,8 @@ def test_dist_cuda2_grid_search_equals_the_brute_force_bit_for_bit():
         "tiny": rng.normal(0, 1, (5, 3)),
         "two_scales": np.concatenate([rng.normal((0, 0, 0), 0.002, (4000, 3)), rng.normal((1, 1, 1), 0.3, (4000, 3))]),
         # translated far from the world origin: the ring search's stop rule works in grid-relative coordinates
-        "translated_1e3": synth.body_points(30_000, seed=1) + np.float32(1.0e3),
-        "translated_1e4": synth.body_points(30_000, seed=2) + np.array([1.0e4, -1.0e4, 3.0e3], np.float32),
+        "translated_1e3": synth.body_points(30_000, seed=1, source="capsule") + np.float32(1.0e3),
+        "translated_1e4": synth.body_points(30_000, seed=2, source="capsule") + np.array([1.0e4, -1.0e4, 3.0e3], np.float32),
     }
     dup = rng.normal(0, 0.2, (3000, 3))
     dup[5] = dup[6]
@@ -245,7 +245,7 @@ def test_dist_cuda2_grid_search_equals_the_brute_force_bit_for_bit():
         grid, brute = distCUDA2(p), distCUDA2(p, brute_force=True)
         assert torch.equal(grid.view(torch.int32), brute.view(torch.int32)), (name, float((grid - brute).abs().max()))
     # configs[3]-sized cloud against the k-d tree, and the point of it: time
-    pts = synth.body_points(500_000, seed=0)
+    pts = synth.body_points(500_000, seed=0, source="capsule")      # (the 20 ms bar was set on this cloud)
     p = torch.from_numpy(pts).cuda()
     distCUDA2(p)
     torch.cuda.synchronize()
@@ -256,6 +256,23 @@ def test_dist_cuda2_grid_search_equals_the_brute_force_bit_for_bit():
     assert np.allclose(got.cpu().numpy(), synth.mean_knn_dist2(pts), rtol=2e-5, atol=1e-12)
     print(f"KNN 500k points: grid {t_grid * 1e3:.2f} ms")
     assert t_grid < 0.02                                  # (the brute force takes ~60 ms here)
+
+
+@pytest.mark.gpu
+def test_dist_cuda2_grid_search_on_the_human_mesh_cloud():
+    """The avatar surface sampled from the local human.obj asset (not shipped: built by humangaussian_amd/data): the grid
+    search returns the brute force's distances bit for bit, and the k-d tree's values."""
+    import numpy as np
+    from humangaussian_amd import data, synth
+    from humangaussian_amd.knn import distCUDA2
+    if not data.have_human_mesh():
+        pytest.skip("the local human.obj asset is missing (humangaussian_amd/data/make_human_mesh.py builds it)")
+    for n, seed in ((100_000, 0), (30_000, 1)):
+        pts = synth.body_points(n, seed=seed, source="human_obj")
+        p = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float32)).cuda()
+        grid, brute = distCUDA2(p), distCUDA2(p, brute_force=True)
+        assert torch.equal(grid.view(torch.int32), brute.view(torch.int32)), (n, float((grid - brute).abs().max()))
+        assert np.allclose(grid.cpu().numpy(), synth.mean_knn_dist2(pts), rtol=2e-5, atol=1e-12), n
 
 
 @pytest.mark.gpu

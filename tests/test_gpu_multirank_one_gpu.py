@@ -45,7 +45,9 @@ def test_bench_two_ranks_on_one_device(vpr):
 @pytest.mark.timeout(900)
 def test_pipelined_view_parallel_step_on_one_device_matches_the_serial_loop(tmp_path):
     """render_views_parallel (HIP rasterizer, 5 views on 2 ranks sharing the device, pipelined rounds) against the same
-    call in ONE process: bit-identical gradients and radii on both ranks."""
+    call in ONE process: bit-identical gradients and radii on both ranks.  The same with a custom render_fn (raw
+    parameters through the activations), also against the serial per-view autograd loop on the raw leaves (bit for bit:
+    the pipelined rounds chain is the serial loop)."""
     script = tmp_path / "vp_worker.py"
     script.write_text('''
 import os, sys, torch, torch.distributed as dist
@@ -64,7 +66,28 @@ def loss_grad(v, color, depth, alpha):
     g = torch.Generator().manual_seed(50 + v)
     return (torch.randn(color.shape, generator=g).cuda(), torch.randn(depth.shape, generator=g).cuda(), torch.randn(alpha.shape, generator=g).cuda())
 grads, radii, _ = vp.render_views_parallel(cams, params, sc["bg"].cuda(), 1, loss_grad, pipeline=True)
-torch.save({"grads": {k: v.cpu() for k, v in grads.items()}, "radii": radii.cpu()}, os.path.join(%r, f"out_{world}_{rank}.pt"))
+# a custom render_fn: the model's raw parameters through sigmoid / exp / normalize (GaussianModel.get_*)
+raw = dict(params, opacities=torch.logit(params["opacities"]), scales=torch.log(params["scales"]),
+           rotations=params["rotations"] * 1.7)
+def act_fn(cam, L, m2, bg, deg):
+    return vp.hip_render_fn(cam, dict(L, opacities=torch.sigmoid(L["opacities"]), scales=torch.exp(L["scales"]),
+                                      rotations=torch.nn.functional.normalize(L["rotations"])), m2, bg, deg)
+agrads, aradii, _ = vp.render_views_parallel(cams, raw, sc["bg"].cuda(), 1, loss_grad, render_fn=act_fn, pipeline=True)
+out = {"grads": {k: v.cpu() for k, v in grads.items()}, "radii": radii.cpu(),
+       "act_grads": {k: v.cpu() for k, v in agrads.items()}, "act_radii": aradii.cpu()}
+if world == 1:          # reference A: per-view autograd on the raw leaves, outside any packed request, summed in view order
+    L = {k: raw[k].detach().requires_grad_(True) for k in raw}
+    names = ("means3D", "shs", "opacities", "scales", "rotations")
+    tot, rmax = None, None
+    for v, cam in enumerate(cams):
+        m2 = torch.zeros_like(L["means3D"], requires_grad=True)
+        c, r, d, a = act_fn(cam, L, m2, sc["bg"].cuda(), 1)
+        gl = torch.autograd.grad([c, d, a], [L[k] for k in names] + [m2], loss_grad(v, c, d, a))
+        g = dict(zip(names + ("means2D",), gl))
+        tot = g if tot is None else {k: tot[k] + g[k] for k in g}
+        rmax = r if rmax is None else torch.maximum(rmax, r)
+    out["ref_grads"], out["ref_radii"] = {k: v.cpu() for k, v in tot.items()}, rmax.cpu()
+torch.save(out, os.path.join(%r, f"out_{world}_{rank}.pt"))
 dist.barrier()
 dist.destroy_process_group()
 ''' % (ROOT, ROOT, str(tmp_path)))
@@ -82,6 +105,11 @@ dist.destroy_process_group()
         assert torch.equal(got["radii"], ref["radii"])
         for k in ref["grads"]:
             assert torch.equal(got["grads"][k], ref["grads"][k]), (r, k)
+    # the custom activation render_fn: the serial autograd loop's bits (reference A), in one process and on both ranks
+    for got in [ref] + [torch.load(tmp_path / f"out_2_{r}.pt") for r in range(2)]:
+        assert torch.equal(got["act_radii"], ref["ref_radii"])
+        for k in ref["ref_grads"]:
+            assert torch.equal(got["act_grads"][k], ref["ref_grads"][k]), k
 
 
 @pytest.mark.timeout(900)
