@@ -165,17 +165,21 @@ class AvatarAnimator:
     """Re-anchor + render of ONE frame on this rank's GPU: `render_frame(vertices, camera)` -> image (3,H,W) in [0,1]
     (`Renderer.render`: gs_renderer.py:923-1028 incl. its clamp), no autograd graph, the frame never leaves the device
     unless the caller moves it.  `gaussians` is any object with the reference GaussianModel getters and a writable
-    `_xyz` (animation.py:403 assigns `self.gs.gaussians._xyz`)."""
+    `_xyz` (animation.py:403 assigns `self.gs.gaussians._xyz`).  antialiasing=True renders every frame with the
+    rasterizer's screen-space antialiasing filter (`Renderer.render(..., antialiasing=True)`): thin structures keep
+    their coverage at resolutions and distances other than the training ones."""
 
-    def __init__(self, gaussians, anchors: MeshAnchoredGaussians, white_background: bool = True, device="cuda"):
+    def __init__(self, gaussians, anchors: MeshAnchoredGaussians, white_background: bool = True, device="cuda",
+                 antialiasing: bool = False):
         from .renderer import Renderer
         self.gaussians, self.anchors = gaussians, anchors
         self.renderer = Renderer(gaussians, white_background=white_background, device=device)
+        self.antialiasing = bool(antialiasing)
 
     @torch.no_grad()
     def render_frame(self, vertices, camera) -> torch.Tensor:
         self.gaussians._xyz = self.anchors.positions(vertices)               # animation.py:384-403, on the device
-        return self.renderer.render(camera)["image"]                         # animation.py:477-482
+        return self.renderer.render(camera, antialiasing=self.antialiasing)["image"]      # animation.py:477-482
 
 
 def orbit_frame_camera(i: int, H: int, W: int, radius: float = 2.0, fovy_deg: float = 50.0, device="cuda"):

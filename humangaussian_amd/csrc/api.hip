@@ -399,7 +399,7 @@ int hgs_pack_view_contribution(int32_t P, int32_t M, const float* g_means3D, con
   return HGS_OK;
 }
 
-int hgs_abi_version(void) { return 16; }
+int hgs_abi_version(void) { return 17; }
 
 size_t hgs_geom_bytes_batch(int32_t B, int32_t P, int32_t H, int32_t W) {
   if (B < 1 || B > HGS_MAX_VIEWS || P < 0 || H <= 0 || W <= 0) return 0;
@@ -444,7 +444,7 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
                                int32_t store_bwd_state, int32_t max_tile_entries_hint, hgs_status* status_host,
                                int32_t status_host_mapped, void* status_event, void* const* stage_events,
                                int32_t activation_flags, float* means2D_leaf, void* stream_) {
-  if (activation_flags & ~(7 | HGS_GRAD_SCALE_TRUE_DERIVATIVE)) return HGS_EINVAL;      // (the gradient bit is the backward's: ignored here)
+  if (activation_flags & ~(7 | HGS_GRAD_SCALE_TRUE_DERIVATIVE | HGS_ANTIALIAS)) return HGS_EINVAL;      // (the gradient bit is the backward's: ignored here)
   if (!batch_ok(s, B) || P < 0 || !out_color || !out_depth || !out_alpha || !geom || !img ||
       entry_capacity < 0)
     return HGS_EINVAL;
@@ -462,7 +462,9 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
   if (entry_capacity > HGS_MAX_ENTRY_CAPACITY) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int ncu = cu_count(stream);
-  // (the gradient bit belongs to the backward: masked out, so that no forward kernel can ever branch on it)
+  // (the gradient bit belongs to the backward: masked out, so that no forward kernel can ever branch on it; the
+  // antialiasing bit selects the forward kernel, not a branch in it)
+  const bool aa = (activation_flags & HGS_ANTIALIAS) != 0;
   const View v = make_view(s, B, P, M, entry_capacity, max_tile_entries_hint > 0 ? max_tile_entries_hint : 0,
                            activation_flags & 7);
   const Layout L = make_layout(geom, bin, img, B, P, v.H, v.W, entry_capacity);
@@ -482,12 +484,12 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
   }
   if (v.nblk > 0) {
     if (v.lds_bins)
-      hipLaunchKernelGGL(hgs_k_preprocess_fwd, dim3(v.B * v.nwg), dim3(HGS_BLOCK), lds_bytes, stream, v,
-                         L, means3D, shs, colors_precomp, opacities, scales, rotations,
+      hipLaunchKernelGGL(aa ? hgs_k_preprocess_fwd_aa : hgs_k_preprocess_fwd, dim3(v.B * v.nwg), dim3(HGS_BLOCK), lds_bytes,
+                         stream, v, L, means3D, shs, colors_precomp, opacities, scales, rotations,
                          cov3D_precomp, radii, means2D_leaf);
     else
-      hipLaunchKernelGGL(hgs_k_preprocess_fwd_ga, dim3(v.B * v.nblk), dim3(HGS_BLOCK), 0, stream, v, L,
-                         means3D, shs, colors_precomp, opacities, scales, rotations,
+      hipLaunchKernelGGL(aa ? hgs_k_preprocess_fwd_ga_aa : hgs_k_preprocess_fwd_ga, dim3(v.B * v.nblk), dim3(HGS_BLOCK), 0,
+                         stream, v, L, means3D, shs, colors_precomp, opacities, scales, rotations,
                          cov3D_precomp, radii, means2D_leaf);
     HGS_LAUNCH_CHECK();
   }
@@ -638,8 +640,8 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
                            float* dL_drotations, float* dL_dcov3D_precomp, void* const* stage_events,
                            int32_t activation_flags, float* pack, int32_t pack_F, void* stream_) {
   (void)radii;
-  if (activation_flags & ~(7 | HGS_GRAD_SCALE_TRUE_DERIVATIVE)) return HGS_EINVAL;
-  if ((activation_flags & HGS_ACT_OPACITY_SIGMOID) && P > 0 && !opacities) return HGS_EINVAL;
+  if (activation_flags & ~(7 | HGS_GRAD_SCALE_TRUE_DERIVATIVE | HGS_ANTIALIAS)) return HGS_EINVAL;
+  if ((activation_flags & (HGS_ACT_OPACITY_SIGMOID | HGS_ANTIALIAS)) && P > 0 && !opacities) return HGS_EINVAL;
   if (!batch_ok(s, B) || P < 0 || !geom || !img || entry_capacity < 0 || entry_capacity > HGS_MAX_ENTRY_CAPACITY) return HGS_EINVAL;
   if (status && status->overflow) return HGS_EINVAL;
   if (status && (int64_t)status->reserved[0] != entry_capacity) return HGS_EINVAL;
@@ -701,6 +703,7 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
   // through LDS (preprocess.hip, mode 2); combinations whose exchange buffer would not fit: the loop.
   const int deg = shs ? v.D : 0;
   const int nc = (deg + 1) * (deg + 1);
+  const int aa = (activation_flags & HGS_ANTIALIAS) ? 1 : 0;   // (the filter's copies of the kernels; d3 switches at run time)
   const unsigned thr_p = 64u * (unsigned)v.B, grid_p = (unsigned)((v.P + 63) / 64);
   const size_t lds_p = (size_t)(23 + 3 * nc) * thr_p * sizeof(float);
   // The exchange buffer may take the CU's whole LDS (160 KB on gfx950; beyond 64 KB the kernel's dynamic-LDS limit is raised
@@ -711,30 +714,35 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
   if (vpar_ok && lds_p > 65536) {
     // the attribute is raised ONCE per (device, kernel) to the CU's whole LDS and remembered: a driver call per backward
     // was host time on the hot path; a refusal is remembered too (and said once on stderr): the loop form then serves
-    static std::atomic<int> lds_raised[64][4];          // 0: not tried, 1: raised to 160 KB, -1: refused
+    static std::atomic<int> lds_raised[64][8];          // [device][deg + 4 aa] 0: not tried, 1: raised to 160 KB, -1: refused
     int dev = 0;
     if (hipStreamGetDevice(stream, &dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int st = lds_raised[dev][deg].load(std::memory_order_relaxed);
+    int st = lds_raised[dev][deg + 4 * aa].load(std::memory_order_relaxed);
     if (st == 0) {
-      const void* kfn = deg == 0 ? reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p0)
-                      : deg == 1 ? reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p1)
-                      : deg == 2 ? reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p2)
-                                 : reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p3);
+      const void* const kfns[8] = {reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p0),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p1),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p2),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p3),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p0_aa),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p1_aa),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p2_aa),
+                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p3_aa)};
+      const void* kfn = kfns[deg + 4 * aa];
       if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) {
         st = 1;
       } else {
         (void)hipGetLastError();
         st = -1;
-        fprintf(stderr, "libhgs_rast: cannot raise the dynamic LDS limit of hgs_k_preprocess_bwd_p%d on device %d: "
-                        "batches that need more than 64 KB take the (slower) loop form\n", deg, dev);
+        fprintf(stderr, "libhgs_rast: cannot raise the dynamic LDS limit of hgs_k_preprocess_bwd_p%d%s on device %d: "
+                        "batches that need more than 64 KB take the (slower) loop form\n", deg, aa ? "_aa" : "", dev);
       }
-      lds_raised[dev][deg].store(st, std::memory_order_relaxed);
+      lds_raised[dev][deg + 4 * aa].store(st, std::memory_order_relaxed);
     }
     if (st < 0) vpar_ok = false;
   }
   const int mode = v.B == 1 ? 1 : (vpar_ok ? 2 : 0);
   const size_t lds_s = hgs_pre_bwd_stage_bytes(M, deg, shs != nullptr && dL_dshs != nullptr);      // (<= 53 KB)
-  switch (deg + 4 * mode) {
+  switch (deg + 4 * mode + 12 * aa) {
     case 0: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d0, v.nblk, HGS_BLOCK, 0); break;
     case 1: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d1, v.nblk, HGS_BLOCK, 0); break;
     case 2: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d2, v.nblk, HGS_BLOCK, 0); break;
@@ -746,7 +754,19 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
     case 8: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p0, grid_p, thr_p, lds_p); break;
     case 9: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p1, grid_p, thr_p, lds_p); break;
     case 10: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p2, grid_p, thr_p, lds_p); break;
-    default: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p3, grid_p, thr_p, lds_p); break;
+    case 11: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p3, grid_p, thr_p, lds_p); break;
+    case 12: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d0_aa, v.nblk, HGS_BLOCK, 0); break;
+    case 13: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d1_aa, v.nblk, HGS_BLOCK, 0); break;
+    case 14: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d2_aa, v.nblk, HGS_BLOCK, 0); break;
+    case 15: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d3, v.nblk, HGS_BLOCK, 0); break;       // (v.act carries the bit)
+    case 16: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s0_aa, v.nblk, HGS_BLOCK, 0); break;
+    case 17: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s1_aa, v.nblk, HGS_BLOCK, lds_s); break;
+    case 18: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s2_aa, v.nblk, HGS_BLOCK, lds_s); break;
+    case 19: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s3_aa, v.nblk, HGS_BLOCK, lds_s); break;
+    case 20: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p0_aa, grid_p, thr_p, lds_p); break;
+    case 21: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p1_aa, grid_p, thr_p, lds_p); break;
+    case 22: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p2_aa, grid_p, thr_p, lds_p); break;
+    default: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p3_aa, grid_p, thr_p, lds_p); break;
   }
 #undef HGS_LAUNCH_PRE_BWD
   HGS_LAUNCH_CHECK();

@@ -98,6 +98,7 @@ struct Proj2D {
   float M00, M01, M02, M10, M11, M12;
   float u0, u1, u2, w0, w1, w2;
   float a, b, c, det;
+  float a0, c0;                // a, c before the 0.3 px^2 dilation
 };
 
 __device__ __forceinline__ void view_point(const float* __restrict__ V, float x, float y,
@@ -131,11 +132,21 @@ __device__ __forceinline__ void project_cov(const Cam& v, const float* __restric
   o.w0 = o.M10 * s.c0 + o.M11 * s.c1 + o.M12 * s.c2;
   o.w1 = o.M10 * s.c1 + o.M11 * s.c3 + o.M12 * s.c4;
   o.w2 = o.M10 * s.c2 + o.M11 * s.c4 + o.M12 * s.c5;
-  o.a = (o.u0 * o.M00 + o.u1 * o.M01 + o.u2 * o.M02) + 0.3f;
+  o.a0 = o.u0 * o.M00 + o.u1 * o.M01 + o.u2 * o.M02;
+  o.a = o.a0 + 0.3f;
   o.b = o.u0 * o.M10 + o.u1 * o.M11 + o.u2 * o.M12;
-  o.c = (o.w0 * o.M10 + o.w1 * o.M11 + o.w2 * o.M12) + 0.3f;
+  o.c0 = o.w0 * o.M10 + o.w1 * o.M11 + o.w2 * o.M12;
+  o.c = o.c0 + 0.3f;
   o.det = o.a * o.c - o.b * o.b;
 }
+
+// Antialiasing (HGS_ANTIALIAS; the screen-space filter of Mip-Splatting, upstream 3DGS's `antialiasing`): the opacity is
+// scaled by rho = sqrt(max(HGS_AA_MIN_RATIO, det(Sigma2D) / det(Sigma2D + 0.3 I))), so that the dilation above adds no
+// coverage.  aa_ratio is rho^2 before the clamp, det(Sigma2D) taken from the UNdilated a0, b, c0 ((a - 0.3)(c - 0.3)
+// would cancel for small Gaussians).  Radii and rects are those of the dilated covariance, as without the filter.
+#define HGS_AA_MIN_RATIO 2.5e-5f
+__device__ __forceinline__ float aa_ratio(const Proj2D& pj) { return (pj.a0 * pj.c0 - pj.b * pj.b) / pj.det; }
+__device__ __forceinline__ float aa_rho(float ratio) { return sqrtf(fmaxf(HGS_AA_MIN_RATIO, ratio)); }
 
 // One Gaussian's (M,3) SH block as 16 B loads into registers.  A thread's block is 12 M bytes
 // (192 B at degree 3), so scalar loads cost 48 uncoalescable instructions per thread; when 3 M is
@@ -253,7 +264,8 @@ __device__ __forceinline__ void eval_sh(int deg, const float* __restrict__ sh, f
 // ------------------------------------------------------------------------------ forward
 namespace {
 
-// Everything stage F1 computes for Gaussian i.  Returns tiles_touched.
+// Everything stage F1 computes for Gaussian i.  Returns tiles_touched.  AA: HGS_ANTIALIAS (rec.op = opacity * rho).
+template <bool AA>
 __device__ __forceinline__ uint32_t preprocess_one(
     const View& v, const Cam& cam, int i, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -306,6 +318,10 @@ __device__ __forceinline__ uint32_t preprocess_one(
   // radii / visibility stay upstream's.
   int tminx = rminx, tminy = rminy, tmaxx = rmaxx, tmaxy = rmaxy;
   hgs_alpha_rect(mx, my, rec.ca, rec.cb, rec.cc, rec.op, tminx, tminy, tmaxx, tmaxy);
+  // antialiasing: the rect above - hence tiles_touched and the tile lists - is cut with the opacity BEFORE the filter, as
+  // upstream keeps its tile counts; it holds the smaller ellipse of op * rho, whose pairs below 1/255 the cell masks and
+  // the blend skip as they always do
+  if (AA) rec.op = rec.op * aa_rho(aa_ratio(pj));
   rec.rect_lo = (uint32_t)tminx | ((uint32_t)tminy << 16);
   rec.rect_hi = (uint32_t)tmaxx | ((uint32_t)tmaxy << 16);
   rec.radius = (int)radf;
@@ -367,12 +383,12 @@ __device__ __forceinline__ void zero_counters(const Layout& L) {
 // LDS-histogram variant (T*4 bytes of dynamic LDS <= 64 KB).  Workgroup (view b, g) owns the
 // Gaussian chunks [g*cpw, (g+1)*cpw) of view b (256 Gaussians each); it counts its tile hits with
 // LDS atomics and writes its histogram ROW hist[b*nwg + g][0..T) - no global atomics per entry.
-extern "C" __global__ void __launch_bounds__(HGS_BLOCK)
-hgs_k_preprocess_fwd(View v, Layout L, const float* __restrict__ means3D,
-                     const float* __restrict__ shs, const float* __restrict__ colors_precomp,
-                     const float* __restrict__ opacities, const float* __restrict__ scales,
-                     const float* __restrict__ rotations,
-                     const float* __restrict__ cov3D_precomp, int32_t* __restrict__ radii, float* __restrict__ zero_leaf) {
+template <bool AA>
+__device__ __forceinline__ void preprocess_fwd_body(
+    const View& v, const Layout& L, const float* __restrict__ means3D, const float* __restrict__ shs,
+    const float* __restrict__ colors_precomp, const float* __restrict__ opacities, const float* __restrict__ scales,
+    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, int32_t* __restrict__ radii,
+    float* __restrict__ zero_leaf) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_hist[];
   __shared__ uint32_t wtot[HGS_BLOCK / 64];
   zero_counters(L);
@@ -388,8 +404,8 @@ hgs_k_preprocess_fwd(View v, Layout L, const float* __restrict__ means3D,
     uint32_t tt = 0;
     if (i < v.P) {
       GeomRec rec;
-      tt = preprocess_one(v, cam, i, means3D, shs, colors_precomp, opacities, scales, rotations,
-                          cov3D_precomp, rec);
+      tt = preprocess_one<AA>(v, cam, i, means3D, shs, colors_precomp, opacities, scales, rotations,
+                              cov3D_precomp, rec);
       radii[(size_t)b * v.P + i] = rec.radius;
       if (zero_leaf) {         // the caller's screen-space leaf [B][P][3] (hgs_forward_batch_act_leaf): zeros, no fill launch
         float* z = zero_leaf + ((size_t)b * v.P + i) * 3;
@@ -413,12 +429,12 @@ hgs_k_preprocess_fwd(View v, Layout L, const float* __restrict__ means3D,
 
 // Fallback for very large images (T*4 > 64 KB): one chunk per workgroup, one global
 // atomic per touched tile.
-extern "C" __global__ void __launch_bounds__(HGS_BLOCK)
-hgs_k_preprocess_fwd_ga(View v, Layout L, const float* __restrict__ means3D,
-                        const float* __restrict__ shs, const float* __restrict__ colors_precomp,
-                        const float* __restrict__ opacities, const float* __restrict__ scales,
-                        const float* __restrict__ rotations,
-                        const float* __restrict__ cov3D_precomp, int32_t* __restrict__ radii, float* __restrict__ zero_leaf) {
+template <bool AA>
+__device__ __forceinline__ void preprocess_fwd_ga_body(
+    const View& v, const Layout& L, const float* __restrict__ means3D, const float* __restrict__ shs,
+    const float* __restrict__ colors_precomp, const float* __restrict__ opacities, const float* __restrict__ scales,
+    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, int32_t* __restrict__ radii,
+    float* __restrict__ zero_leaf) {
   __shared__ uint32_t wtot[HGS_BLOCK / 64];
   zero_counters(L);
   const int b = (int)blockIdx.x / v.nblk, chunk = (int)blockIdx.x % v.nblk;
@@ -427,8 +443,8 @@ hgs_k_preprocess_fwd_ga(View v, Layout L, const float* __restrict__ means3D,
   uint32_t tt = 0;
   if (i < v.P) {
     GeomRec rec;
-    tt = preprocess_one(v, cam, i, means3D, shs, colors_precomp, opacities, scales, rotations,
-                        cov3D_precomp, rec);
+    tt = preprocess_one<AA>(v, cam, i, means3D, shs, colors_precomp, opacities, scales, rotations,
+                            cov3D_precomp, rec);
     radii[(size_t)b * v.P + i] = rec.radius;
     if (zero_leaf) {
       float* z = zero_leaf + ((size_t)b * v.P + i) * 3;
@@ -447,6 +463,20 @@ hgs_k_preprocess_fwd_ga(View v, Layout L, const float* __restrict__ means3D,
   if (i < v.P && tt) L.geom[(size_t)b * v.P + i].offset = off;
 }
 
+// the forward kernels: without (the default) and with the antialiasing filter (HGS_ANTIALIAS)
+#define HGS_PRE_FWD_KERNEL(NAME, BODY, AA)                                                                       \
+  extern "C" __global__ void __launch_bounds__(HGS_BLOCK) NAME(                                                  \
+      View v, Layout L, const float* __restrict__ means3D, const float* __restrict__ shs,                        \
+      const float* __restrict__ colors_precomp, const float* __restrict__ opacities,                             \
+      const float* __restrict__ scales, const float* __restrict__ rotations,                                     \
+      const float* __restrict__ cov3D_precomp, int32_t* __restrict__ radii, float* __restrict__ zero_leaf) {     \
+    BODY<AA>(v, L, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, zero_leaf);   \
+  }
+HGS_PRE_FWD_KERNEL(hgs_k_preprocess_fwd, preprocess_fwd_body, false)
+HGS_PRE_FWD_KERNEL(hgs_k_preprocess_fwd_ga, preprocess_fwd_ga_body, false)
+HGS_PRE_FWD_KERNEL(hgs_k_preprocess_fwd_aa, preprocess_fwd_body, true)
+HGS_PRE_FWD_KERNEL(hgs_k_preprocess_fwd_ga_aa, preprocess_fwd_ga_body, true)
+
 // ----------------------------------------------------------------------------- backward
 // One thread per Gaussian.  For every view of the batch, in view order: sums the Gaussian's
 // tiles_touched gradient rows (contiguous, fixed order => deterministic), then chains through
@@ -462,7 +492,9 @@ namespace {
 // them through LDS and wave 0 adds them in view order (the same sequence of fp32 additions as the loop of
 // mode 0) and writes the outputs.  B times the threads of mode 0, none of
 // which carries sums across a loop: the 8-view backward was a latency chain of 1.5 waves per SIMD.
-template <int DEG, int MODE>
+// AA: the antialiasing filter's chain rule (HGS_ANTIALIAS); 0: off, 1: on, 2: decided at run time from v.act (the one
+// form whose compile-time copy would not fit its registers: the loop over the views at SH degree 3).
+template <int DEG, int MODE, int AA>
 __device__ __forceinline__ void preprocess_bwd_body(
     const View& v, const Layout& L, const hgs_status* __restrict__ status,
     const float* __restrict__ grad_rows, const float* __restrict__ means3D,
@@ -502,6 +534,7 @@ __device__ __forceinline__ void preprocess_bwd_body(
   if (!mine) i = 0;                               // mode 2: idle threads stay for the barrier; they read Gaussian 0 of
   if (bview >= v.B) bview = 0;                    // view 0 (the view stays wave-uniform) and write nothing
   const bool ok = status->overflow == 0;
+  const bool aa = AA == 1 || (AA == 2 && (v.act & HGS_ANTIALIAS) != 0);
 
   // ---- view-independent inputs.  One view: loaded once.  Several views: RE-loaded at the top of every
   // view iteration behind a compiler barrier - they come from L1/L2, and keeping them (and what the
@@ -587,7 +620,7 @@ __device__ __forceinline__ void preprocess_bwd_body(
           }
         }
       }
-      a_op += gop;
+      if (!aa) a_op += gop;
       a_col[0] += gr; a_col[1] += gg; a_col[2] += gb;
 
       Proj2D pj;
@@ -597,9 +630,21 @@ __device__ __forceinline__ void preprocess_bwd_body(
       // ---- conic -> cov2D (a, b, c)
       const float a = pj.a, bq_ = pj.b, c = pj.c;
       const float inv2 = 1.0f / (pj.det * pj.det);
-      const float dLa = inv2 * (-c * c * gA + bq_ * c * gB - bq_ * bq_ * gC);
-      const float dLb = inv2 * (2.0f * bq_ * c * gA - (pj.det + 2.0f * bq_ * bq_) * gB + 2.0f * a * bq_ * gC);
-      const float dLc = inv2 * (-bq_ * bq_ * gA + a * bq_ * gB - a * a * gC);
+      float dLa = inv2 * (-c * c * gA + bq_ * c * gB - bq_ * bq_ * gC);
+      float dLb = inv2 * (2.0f * bq_ * c * gA - (pj.det + 2.0f * bq_ * bq_) * gB + 2.0f * a * bq_ * gC);
+      float dLc = inv2 * (-bq_ * bq_ * gA + a * bq_ * gB - a * a * gC);
+      if (aa) {
+        // ---- antialiasing: gop is dL/d(opacity rho).  rho^2 = det0 / det with det0 = a0 c0 - b^2, det = a c - b^2,
+        // a = a0 + 0.3, c = c0 + 0.3; under the clamp rho is a constant
+        const float ratio = aa_ratio(pj), rho = aa_rho(ratio);
+        a_op += gop * rho;
+        if (ratio > HGS_AA_MIN_RATIO) {
+          const float k = gop * act_opacity(opacities_raw[i], v.act) / (2.0f * rho * pj.det);
+          dLa += k * (pj.c0 - ratio * c);
+          dLc += k * (pj.a0 - ratio * a);
+          dLb += -2.0f * k * bq_ * (1.0f - ratio);
+        }
+      }
 
       // ---- cov2D -> packed cov3D
       const float M0[3] = {pj.M00, pj.M01, pj.M02}, M1[3] = {pj.M10, pj.M11, pj.M12};
@@ -939,7 +984,7 @@ __device__ __forceinline__ void preprocess_bwd_body(
 
 }  // namespace
 
-#define HGS_PRE_BWD_KERNEL(DEG, NAME, MODE, THREADS)                                                     \
+#define HGS_PRE_BWD_KERNEL(DEG, NAME, MODE, THREADS, AA)                                                 \
   extern "C" __global__ void __launch_bounds__(THREADS) NAME(                                       \
       View v, Layout L, const hgs_status* __restrict__ status, const float* __restrict__ grad_rows, \
       const float* __restrict__ means3D, const float* __restrict__ shs,                             \
@@ -949,22 +994,34 @@ __device__ __forceinline__ void preprocess_bwd_body(
       float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dshs, \
       float* __restrict__ dL_dcolors, float* __restrict__ dL_dopac, float* __restrict__ dL_dscales,  \
       float* __restrict__ dL_drots, float* __restrict__ dL_dcov3D, float* __restrict__ pack, int pack_F) { \
-    preprocess_bwd_body<DEG, MODE>(v, L, status, grad_rows, means3D, shs, colors_precomp, opacities_raw, scales, \
+    preprocess_bwd_body<DEG, MODE, AA>(v, L, status, grad_rows, means3D, shs, colors_precomp, opacities_raw, scales, \
                              rotations, cov3D_precomp, dL_dmeans3D, dL_dmeans2D, dL_dshs,           \
                              dL_dcolors, dL_dopac, dL_dscales, dL_drots, dL_dcov3D, pack, pack_F);  \
   }
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_d0, 0, HGS_BLOCK)         // thread per Gaussian, loop over the views
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_d1, 0, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_d2, 0, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_d3, 0, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_s0, 1, HGS_BLOCK)         // single-view instantiations
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_s1, 1, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_s2, 1, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_s3, 1, HGS_BLOCK)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_p0, 2, 1024)   // thread per (Gaussian, view): up to 16 views (SH degree >= 2: 8, registers / LDS)
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_p1, 2, 1024)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_p2, 2, 512)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_p3, 2, 512)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_d0, 0, HGS_BLOCK, 0)         // thread per Gaussian, loop over the views
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_d1, 0, HGS_BLOCK, 0)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_d2, 0, HGS_BLOCK, 0)
+HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_d3, 0, HGS_BLOCK, 2)         // (antialiasing: a run-time switch, see above)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_s0, 1, HGS_BLOCK, 0)         // single-view instantiations
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_s1, 1, HGS_BLOCK, 0)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_s2, 1, HGS_BLOCK, 0)
+HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_s3, 1, HGS_BLOCK, 0)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_p0, 2, 1024, 0)   // thread per (Gaussian, view): up to 16 views (SH degree >= 2: 8, registers / LDS)
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_p1, 2, 1024, 0)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_p2, 2, 512, 0)
+HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_p3, 2, 512, 0)
+// with the antialiasing filter (HGS_ANTIALIAS): compile-time copies of every form but the SH-3 loop (d3 above)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_d0_aa, 0, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_d1_aa, 0, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_d2_aa, 0, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_s0_aa, 1, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_s1_aa, 1, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_s2_aa, 1, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_s3_aa, 1, HGS_BLOCK, 1)
+HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_p0_aa, 2, 1024, 1)
+HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_p1_aa, 2, 1024, 1)
+HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_p2_aa, 2, 512, 1)
+HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_p3_aa, 2, 512, 1)
 
 // ------------------------------------------------------------------------- mark visible
 extern "C" __global__ void __launch_bounds__(HGS_BLOCK)

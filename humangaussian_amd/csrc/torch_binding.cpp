@@ -218,7 +218,8 @@ std::vector<std::pair<Tensor, int64_t>> g_pack_saved;     // slot + count of eac
 struct Rasterize : public torch::autograd::Function<Rasterize> {
   // 22 arguments after ctx (backward returns one slot per argument).  `tanfov` is a CPU double
   // tensor [2][B] (x row, y row); `batch` = 0 for the single-view API, else the number of views;
-  // `act` = HGS_ACT_* bits (raw parameters in, activations fused into the per-Gaussian kernels).
+  // `act` = HGS_ACT_* bits (raw parameters in, activations fused into the per-Gaussian kernels) and HGS_ANTIALIAS; the
+  // plan keeps them for the backward (whichever it runs: the bit must reach it as it reached the forward).
   static variable_list forward(AutogradContext* ctx, const Tensor& means3D, const Tensor& means2D,
                                const Tensor& sh, const Tensor& colors_precomp, const Tensor& opacities,
                                const Tensor& scales, const Tensor& rotations, const Tensor& cov3D,
@@ -535,18 +536,20 @@ Tensor tanfov_tensor(const std::vector<double>& x, const std::vector<double>& y)
   return t;
 }
 
-// single view: the signature of upstream's _C.rasterize_gaussians call
+// single view: the signature of upstream's _C.rasterize_gaussians call, plus the library's flag bits (HGS_ANTIALIAS;
+// 0 = upstream's behaviour)
 std::vector<Tensor> rasterize(const Tensor& means3D, const Tensor& means2D, const c10::optional<Tensor>& sh,
                               const c10::optional<Tensor>& colors_precomp, const Tensor& opacities,
                               const c10::optional<Tensor>& scales, const c10::optional<Tensor>& rotations,
                               const c10::optional<Tensor>& cov3D, const Tensor& bg, const Tensor& viewmatrix,
                               const Tensor& projmatrix, const Tensor& campos, int64_t H, int64_t W, double tanfovx,
                               double tanfovy, double scale_modifier, int64_t sh_degree, bool prefiltered, bool debug,
-                              bool want_grad, bool zero_means2D) {
+                              bool want_grad, bool zero_means2D, int64_t activation_flags) {
+  if (activation_flags & ~(int64_t)0xffff) throw std::runtime_error("rasterize: unknown activation_flags bits");
   return Rasterize::apply(means3D, means2D, opt(sh), opt(colors_precomp), opacities, opt(scales), opt(rotations),
                           opt(cov3D), bg, viewmatrix, projmatrix, campos, tanfov_tensor({tanfovx}, {tanfovy}), H, W,
                           scale_modifier, sh_degree, prefiltered, debug, want_grad, (int64_t)0,
-                          (int64_t)(zero_means2D ? (1 << 16) : 0));
+                          activation_flags | (int64_t)(zero_means2D ? (1 << 16) : 0));
 }
 
 // B views in one launch set: bg (3) or (B,3), viewmatrix / projmatrix (B,4,4), campos (B,3), means2D (B,P,3);

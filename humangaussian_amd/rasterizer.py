@@ -66,12 +66,21 @@ def _state(device: torch.device):
     return ns
 
 
+def _settings_antialiasing(raster_settings) -> bool:
+    # upstream's newer settings carry a 13th field `antialiasing`; GaussianRasterizationSettings keeps the fork's 12
+    return bool(getattr(raster_settings, "antialiasing", False))
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                        cov3Ds_precomp, raster_settings, zero_means2D: bool = False):
+                        cov3Ds_precomp, raster_settings, zero_means2D: bool = False,
+                        antialiasing: Optional[bool] = None):
     """Replaces upstream's `_RasterizeGaussians.apply` (forward -> `_C.rasterize_gaussians`,
     backward -> `_C.rasterize_gaussians_backward`).
     zero_means2D: `means2D` is UNINITIALISED storage (`torch.empty`); the forward's per-Gaussian kernel writes the zeros
-    upstream's `torch.zeros_like(xyz) + 0` holds (ABI v16, `hgs_forward_batch_act_leaf`) - no fill launch."""
+    upstream's `torch.zeros_like(xyz) + 0` holds (ABI v16, `hgs_forward_batch_act_leaf`) - no fill launch.
+    antialiasing: upstream 3DGS's screen-space filter (ANTIALIAS, include/hgs_rast.h: HGS_ANTIALIAS); None (the default)
+    follows the settings object (`antialiasing`, a field of upstream's newer settings; absent = off), True / False
+    override it."""
     want_grad = torch.is_grad_enabled() and (
         means3D.requires_grad or means2D.requires_grad or opacities.requires_grad
         or (sh is not None and sh.requires_grad)
@@ -80,15 +89,18 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         or (rotations is not None and rotations.requires_grad)
         or (cov3Ds_precomp is not None and cov3Ds_precomp.requires_grad))
     rs = raster_settings
+    aa = _settings_antialiasing(rs) if antialiasing is None else bool(antialiasing)
     color, radii, depth, alpha = _lib.load_binding().rasterize(
         means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
         rs.bg, rs.viewmatrix, rs.projmatrix, rs.campos, int(rs.image_height), int(rs.image_width),
         float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree),
-        bool(rs.prefiltered), bool(rs.debug), want_grad, bool(zero_means2D))
+        bool(rs.prefiltered), bool(rs.debug), want_grad, bool(zero_means2D), ANTIALIAS if aa else 0)
     return color, radii, depth, alpha
 
 
 ACT_OPACITY_SIGMOID, ACT_SCALE_EXP, ACT_ROTATION_NORMALIZE = 1, 2, 4      # HGS_ACT_* of include/hgs_rast.h
+# opt-in antialiasing (HGS_ANTIALIAS): opacity x sqrt(max(2.5e-5, det(cov2D) / det(cov2D + 0.3 I))), forward and backward
+ANTIALIAS = 16
 # the torch binding's own bit (stripped before the library sees the flags): `means2D` is uninitialised storage, the
 # forward zero-fills it inside its per-Gaussian kernel (see rasterize_gaussians)
 ZERO_MEANS2D = 1 << 16
@@ -98,7 +110,8 @@ GRAD_SCALE_TRUE_DERIVATIVE = 8
 
 
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                              cov3Ds_precomp, raster_settings_list, activation_flags: int = 0):
+                              cov3Ds_precomp, raster_settings_list, activation_flags: int = 0,
+                              antialiasing: Optional[bool] = None):
     """B views of the same Gaussians in ONE launch set (include/hgs_rast.h: hgs_forward_batch /
     hgs_backward_batch) - what the reference does with a Python loop over
     `render()` at threestudio/systems/GaussianDreamer.py:244-266.
@@ -111,6 +124,9 @@ def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, s
                           (`_opacity` logits, `_scaling` log-scales, un-normalised `_rotation`) and
                           sigmoid / exp / normalize (scene/gaussian_model.py:95-115) run inside the
                           per-Gaussian kernels, forward and backward; gradients are w.r.t. the raw tensors
+    antialiasing          the screen-space filter for every view (the ANTIALIAS bit of activation_flags); None (the
+                          default) follows the bit or, without it, the settings objects' `antialiasing` - which must
+                          agree across the views - and True / False override both
     Returns color (B,3,H,W), radii (B,P) int32, depth (B,1,H,W), alpha (B,1,H,W); every view is
     bit-identical to a separate single-view call, parameter gradients are the sum over the views."""
     rsl = list(raster_settings_list)
@@ -121,6 +137,11 @@ def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, s
         if (int(rs.image_height), int(rs.image_width), int(rs.sh_degree), float(rs.scale_modifier)) != \
                 (int(r0.image_height), int(r0.image_width), int(r0.sh_degree), float(r0.scale_modifier)):
             raise ValueError("all views of a batch must share image size, sh_degree and scale_modifier")
+        if _settings_antialiasing(rs) != _settings_antialiasing(r0):
+            raise ValueError("all views of a batch must agree in antialiasing")
+    if antialiasing is None:
+        antialiasing = bool(int(activation_flags) & ANTIALIAS) or _settings_antialiasing(r0)
+    activation_flags = (int(activation_flags) & ~ANTIALIAS) | (ANTIALIAS if antialiasing else 0)
     B = len(rsl)
     dev = means3D.device
     if B == 1:          # (views of the caller's tensors: no stack kernels in front of a single view)
@@ -182,9 +203,13 @@ class _RasterizeGaussians:
 # --------------------------------------------------------------------------- the module
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    """antialiasing: upstream 3DGS's screen-space filter (ANTIALIAS); None = what the settings object says
+    (`antialiasing`, a field of upstream's newer settings; False for GaussianRasterizationSettings)."""
+
+    def __init__(self, raster_settings: GaussianRasterizationSettings, antialiasing: Optional[bool] = None):
         super().__init__()
         self.raster_settings = raster_settings
+        self.antialiasing = antialiasing          # None: the settings object decides (rasterize_gaussians)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test (replaces `_C.mark_visible`)."""
@@ -205,4 +230,5 @@ class GaussianRasterizer(nn.Module):
                             'precomputed 3D covariance!')
         # upstream turns missing optionals into empty tensors for its `_C`; the binding takes None
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales,
-                                   rotations, cov3D_precomp, raster_settings, zero_means2D=zero_means2D)
+                                   rotations, cov3D_precomp, raster_settings, zero_means2D=zero_means2D,
+                                   antialiasing=self.antialiasing)

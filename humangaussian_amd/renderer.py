@@ -7,6 +7,8 @@
 
 `viewpoint_camera` / `pc` / `pipe` are duck-typed exactly like the reference objects
 (`scene/cameras.py:17-67`, `scene/gaussian_model.py:95-118`, `arguments/__init__.py:63-68`).
+`pipe.antialiasing = True` (where upstream 3DGS's `PipelineParams` keeps the switch; absent = off) turns on the
+rasterizer's screen-space antialiasing filter (include/hgs_rast.h: HGS_ANTIALIAS).
 """
 from __future__ import annotations
 
@@ -84,8 +86,8 @@ FUSE_ACTIVATIONS = False
 
 
 def _render_fused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, screenspace_points, settings,
-                  zero_in_kernel=False):
-    from .rasterizer import (ACT_OPACITY_SIGMOID, ACT_ROTATION_NORMALIZE, ACT_SCALE_EXP, ZERO_MEANS2D,
+                  zero_in_kernel=False, antialiasing=False):
+    from .rasterizer import (ACT_OPACITY_SIGMOID, ACT_ROTATION_NORMALIZE, ACT_SCALE_EXP, ANTIALIAS, ZERO_MEANS2D,
                              rasterize_gaussians_batch)
     f = lambda t: None if t is None else t.float()  # noqa: E731
     shs = None
@@ -97,7 +99,8 @@ def _render_fused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, overri
     image, radii, depth, alpha = rasterize_gaussians_batch(
         f(pc.get_xyz), f(screenspace_points).unsqueeze(0), f(shs), f(override_color), f(pc._opacity), f(pc._scaling),
         f(pc._rotation), None, [settings],
-        activation_flags=ACT_OPACITY_SIGMOID | ACT_SCALE_EXP | ACT_ROTATION_NORMALIZE | (ZERO_MEANS2D if zero_in_kernel else 0))
+        activation_flags=ACT_OPACITY_SIGMOID | ACT_SCALE_EXP | ACT_ROTATION_NORMALIZE | (ZERO_MEANS2D if zero_in_kernel else 0)
+        | (ANTIALIAS if antialiasing else 0))
     # (squeeze, not [0]: a select's backward zero-fills and copies a full-size gradient per output)
     return image.squeeze(0), radii.squeeze(0), depth.squeeze(0), alpha.squeeze(0)
 
@@ -121,14 +124,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         prefiltered=False,
         debug=bool(getattr(pipe, "debug", False)),
     )
+    antialiasing = bool(getattr(pipe, "antialiasing", False))
     fuse = FUSE_ACTIVATIONS if fuse_activations is None else bool(fuse_activations)
     if fuse and not getattr(pipe, "compute_cov3D_python", False) and not getattr(pipe, "convert_SHs_python", False) and \
             all(hasattr(pc, a) for a in ("_opacity", "_scaling", "_rotation")):
         rendered_image, radii, depth, alpha = _render_fused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier,
-                                                            override_color, screenspace_points, raster_settings, zero_in_kernel)
+                                                            override_color, screenspace_points, raster_settings, zero_in_kernel,
+                                                            antialiasing)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                 "radii": radii, "depth_3dgs": depth, "alpha_3dgs": alpha}
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, antialiasing=antialiasing)
 
     means3D = pc.get_xyz
     opacity = pc.get_opacity
@@ -175,13 +180,14 @@ class Renderer:
                                      dtype=torch.float32, device=device)
 
     def render(self, viewpoint_camera, scaling_modifier=1.0, bg_color=None, override_color=None,
-               compute_cov3D_python=False, convert_SHs_python=False, fuse_activations=None):
+               compute_cov3D_python=False, convert_SHs_python=False, fuse_activations=None, antialiasing=False):
         class _Pipe:
             pass
         pipe = _Pipe()
         pipe.compute_cov3D_python = compute_cov3D_python
         pipe.convert_SHs_python = convert_SHs_python
         pipe.debug = False
+        pipe.antialiasing = bool(antialiasing)
         out = render(viewpoint_camera, self.gaussians, pipe,
                      self.bg_color if bg_color is None else bg_color, scaling_modifier,
                      override_color, fuse_activations=fuse_activations)
@@ -253,6 +259,7 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color: torch.Tensor, scaling_mo
     `pc._rotation`) to the rasterizer, which applies sigmoid / exp / normalize inside its
     per-Gaussian kernels (forward and backward): six elementwise launches fewer per step; results
     then agree with the un-fused path to rounding (expf vs torch.exp), not bit for bit.
+    `pipe.antialiasing = True` turns on the screen-space antialiasing filter, as in render().
 
     `viewpoint_cameras`: reference `Camera` / `MiniCam` objects, or the `HostCamera`s of `cameras_from_c2w()` (host-side
     matrices, one upload per step instead of the reference's per-view device inversions).
@@ -277,8 +284,10 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color: torch.Tensor, scaling_mo
         sh_degree=pc.active_sh_degree, campos=c.camera_center, prefiltered=False,
         debug=bool(getattr(pipe, "debug", False))) for i, c in enumerate(cams)]
 
-    from .rasterizer import ZERO_MEANS2D
+    from .rasterizer import ANTIALIAS, ZERO_MEANS2D
     act = ZERO_MEANS2D if zero_in_kernel else 0
+    if getattr(pipe, "antialiasing", False):
+        act |= ANTIALIAS
     fuse = bool(fuse_activations) and not getattr(pipe, "compute_cov3D_python", False) and \
         all(hasattr(pc, a) for a in ("_opacity", "_scaling", "_rotation"))
     scales = rotations = cov3D_precomp = None

@@ -186,6 +186,16 @@ int hgs_backward_batch(const hgs_settings* views, int32_t B, int32_t P, int32_t 
  * the reference passes: gaussian_renderer/__init__.py:18, gs_renderer.py:925).  With this bit set dL_dscales is the
  * true derivative dL/dscale = mod * dL/d(mod * scale). */
 #define HGS_GRAD_SCALE_TRUE_DERIVATIVE 8
+/* v17, opt-in antialiasing: the screen-space filter of Mip-Splatting (upstream 3DGS's `antialiasing` switch).  Every
+ * projected covariance gets the 0.3 px^2 dilation as always; with this bit each Gaussian's opacity is also scaled by
+ *   rho = sqrt(max(2.5e-5, det(Sigma2D) / det(Sigma2D + 0.3 I)))
+ * so that the dilation adds no coverage (radii, tile rects and tiles_touched stay exactly as without the bit: the rects are
+ * cut with the opacity before the factor).  dL_dopacities is then
+ * the gradient w.r.t. the opacity before the factor, and the backward carries rho's dependence on the covariance into
+ * the mean, scale, rotation and cov3D gradients.  Accepted by hgs_forward_batch_act(_leaf), hgs_backward_batch_act and
+ * hgs_backward_batch_packed.  Like entry_capacity, the bit must be the SAME in the forward and the backward of a call
+ * (the backward recomputes rho; it does not check the forward's choice); the backward with it needs `opacities`. */
+#define HGS_ANTIALIAS 16
 int hgs_forward_batch_act(const hgs_settings* views, int32_t B, int32_t P, int32_t M,
                           const float* means3D, const float* shs, const float* colors_precomp,
                           const float* opacities, const float* scales, const float* rotations,
@@ -230,7 +240,8 @@ int hgs_backward_batch_act(const hgs_settings* views, int32_t B, int32_t P, int3
  * the blend backward is launched with the capacity-derived upper bound of workgroups
  * (entry_capacity/64 + tiles) and every kernel reads the device-side status (an
  * overflowed forward yields all-zero gradients).  `entry_capacity` must equal the value
- * given to hgs_forward (it fixes the carve of `bin`), bwd_scratch must hold
+ * given to hgs_forward (it fixes the carve of `bin`); so must the HGS_ANTIALIAS bit of the *_act
+ * entry points (the backward recomputes the filter's factor from it), bwd_scratch must hold
  * hgs_bwd_scratch_bytes(num_rendered) - or (entry_capacity) when status is NULL - or, when
  * status->num_pairs is non-zero, hgs_bwd_scratch_bytes_pairs(num_rendered, status->num_pairs):
  * status->num_pairs DECLARES how many pair rows the scratch holds (0 = the worst case of 16 per
