@@ -93,6 +93,11 @@ EXPORTS = {
     "hgs_compact_index": (ctypes.c_int, [c_int32] + [c_void_p] * 5),
     "hgs_gather_rows": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 4),
     "hgs_reanchor": (ctypes.c_int, [c_int32] + [c_void_p] * 7),
+    "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
+    "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgs_mesh_query": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -159,6 +159,29 @@ def human_mesh_anchors(n: int, seed: int = 0, device="cuda", max_dist: float = 0
     return mv, MeshAnchoredGaussians(f, tri.astype(np.int32), uvw, dist_, device=device)
 
 
+def anchor_to_mesh(points, vertices, faces, max_error: float = 0.01):
+    """Anchor a trained avatar's Gaussians on its body mesh the way the reference does once per avatar
+    (/root/reference/animation.py:337-371): a "raystab" signed-distance query (`mesh.MeshIndex`, the HIP stand-in for
+    cubvh), the rebuild closest + dist * unit face normal at the rest pose (hgs_reanchor, the pass every frame runs),
+    err = |rebuilt - points| and keep = ~(err > max_error), the reference's own culling test.  Rows of non-finite points
+    (face -1) are never kept, and their rebuild does not index a face.
+    Returns (MeshAnchoredGaussians of the KEPT rows, keep (P,) bool, err (P,) fp32), all on the points' device."""
+    from .mesh import MeshIndex
+    pts = torch.as_tensor(points)
+    if pts.device.type != "cuda":
+        raise RuntimeError("humangaussian_amd: points must live on a HIP device (there is no CPU path)")
+    pts = pts.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    index = MeshIndex(vertices, faces, device=pts.device)
+    dist_, face, uvw = index.signed_distance(pts, return_uvw=True, mode="raystab")
+    found = face >= 0
+    face32 = torch.where(found, face, torch.zeros_like(face)).to(torch.int32)
+    rebuilt = _lib.load_binding().reanchor(index.vertices, index.faces, face32, uvw, torch.where(found, dist_, 0.0))
+    err = torch.where(found, torch.linalg.vector_norm(rebuilt - pts, dim=-1), float("nan"))
+    keep = ~(err > max_error) & found
+    anchors = MeshAnchoredGaussians(index.faces, face32[keep], uvw[keep], dist_[keep], device=pts.device)
+    return anchors, keep, err
+
+
 # ------------------------------------------------------------------------------ one frame, and the sharded loop
 
 class AvatarAnimator:
@@ -175,6 +198,19 @@ class AvatarAnimator:
         self.gaussians, self.anchors = gaussians, anchors
         self.renderer = Renderer(gaussians, white_background=white_background, device=device)
         self.antialiasing = bool(antialiasing)
+
+    @classmethod
+    def from_rest_pose(cls, gaussians, vertices, faces, max_error: float = 0.01, **kw) -> "AvatarAnimator":
+        """The animator of a trained avatar: `anchor_to_mesh(gaussians.get_xyz, vertices, faces, max_error)` on its rest-pose
+        body mesh, then the culling of the reference (animation.py:365-371): the six tensors `_xyz`, `_features_dc`,
+        `_features_rest`, `_opacity`, `_scaling` and `_rotation` keep only the anchored rows (in place on `gaussians`).
+        `keep` and `anchor_error` stay on the returned animator; **kw go to the constructor."""
+        anchors, keep, err = anchor_to_mesh(gaussians.get_xyz.detach(), vertices, faces, max_error=max_error)
+        for name in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
+            setattr(gaussians, name, getattr(gaussians, name)[keep])
+        anim = cls(gaussians, anchors, **kw)
+        anim.keep, anim.anchor_error = keep, err
+        return anim
 
     @torch.no_grad()
     def render_frame(self, vertices, camera) -> torch.Tensor:

@@ -22,6 +22,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "binning.hip"
 #include "render_fwd.hip"
 #include "knn.hip"
+#include "mesh.hip"
 #include "bookkeeping.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
@@ -922,6 +923,101 @@ int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const i
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_reanchor, dim3((P + 255) / 256), dim3(256), 0, stream, (int)P, vertices, faces, mapping_face,
                      mapping_uvw, mapping_dist, xyz);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+namespace {
+struct MeshCarve { size_t tris, start, cursor, bsum, refs, total; };
+MeshCarve carve_mesh(int32_t F, uint32_t ncells, uint64_t nrefs) {
+  MeshCarve c;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  take(sizeof(MeshGridHdr));
+  c.tris = take((size_t)F * 48);
+  c.start = take(((size_t)ncells + 1) * 4);
+  c.cursor = take((size_t)ncells * 4);
+  c.bsum = take(((size_t)ncells / 1024 + 2) * 4);
+  c.refs = take((size_t)nrefs * 4);
+  c.total = off;
+  return c;
+}
+bool mesh_info_ok(const hgs_mesh_grid_info* in) {
+  if (!in || in->num_faces < 1 || in->num_refs > 0x7fffffffull || !(in->cell > 0.0f)) return false;
+  unsigned long long n = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (in->dims[a] < 1 || in->dims[a] > 4096) return false;
+    n *= (unsigned long long)in->dims[a];
+  }
+  return n == in->ncells && n <= HGS_MESH_MAX_CELLS;
+}
+}  // namespace
+
+int hgs_mesh_grid_plan(int32_t V, const float* vertices, int32_t F, const int32_t* faces, hgs_mesh_grid_info* info,
+                       void* stream_) {
+  if (V < 0 || F < 1 || !info || !faces || (V > 0 && !vertices)) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipError_t e = hipMemsetAsync(info, 0, sizeof(hgs_mesh_grid_info), stream);
+  if (e == hipSuccess) e = hipMemsetAsync(&info->bmin[0], 0xff, 12, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  if (V > 0) hipLaunchKernelGGL(hgs_k_mesh_bbox, dim3((V + 255) / 256), dim3(256), 0, stream, (int)V, vertices, info);
+  hipLaunchKernelGGL(hgs_k_mesh_grid_setup, dim3(1), dim3(64), 0, stream, (int)F, info);
+  hipLaunchKernelGGL(hgs_k_mesh_count_refs, dim3((F + 255) / 256), dim3(256), 0, stream, (int)V, vertices, (int)F, faces, info);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+size_t hgs_mesh_grid_bytes(const hgs_mesh_grid_info* info_host) {
+  if (!mesh_info_ok(info_host)) return 0;
+  return carve_mesh(info_host->num_faces, info_host->ncells, info_host->num_refs).total;
+}
+
+int hgs_mesh_grid_build(int32_t V, const float* vertices, int32_t F, const int32_t* faces,
+                        const hgs_mesh_grid_info* info_host, void* grid, void* stream_) {
+  if (V < 0 || F < 1 || !faces || !grid || (V > 0 && !vertices) || !mesh_info_ok(info_host) || info_host->num_faces != F)
+    return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hgs_mesh_grid_info& in = *info_host;
+  const MeshCarve c = carve_mesh(F, in.ncells, in.num_refs);
+  MeshGridHdr G;
+  G.gx = in.dims[0]; G.gy = in.dims[1]; G.gz = in.dims[2];
+  G.ncells = in.ncells;
+  G.ox = in.origin[0]; G.oy = in.origin[1]; G.oz = in.origin[2];
+  G.h = in.cell;
+  G.inv_h = 1.0f / in.cell;            // (the plan's count_refs divides the same way)
+  G.cmax = 0.0f;
+  for (int a = 0; a < 3; ++a)
+    G.cmax = std::max(G.cmax, std::max(fabsf(in.origin[a]), fabsf(in.origin[a] + (float)in.dims[a] * in.cell)));
+  G.F = F;
+  G.nrefs = (uint32_t)in.num_refs;
+  G.off_tris = c.tris; G.off_start = c.start; G.off_cursor = c.cursor; G.off_bsum = c.bsum; G.off_refs = c.refs;
+  const unsigned long long n_init = std::max<unsigned long long>((unsigned long long)in.ncells + 1, (unsigned long long)F);
+  const unsigned gf = (unsigned)((F + 255) / 256), gc = (in.ncells + 1023u) / 1024u;
+  hipLaunchKernelGGL(hgs_k_mesh_grid_init, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, stream, G, (int)V,
+                     vertices, faces, grid);
+  hipLaunchKernelGGL(hgs_k_mesh_bin, dim3(gf), dim3(256), 0, stream, G, grid, 0);
+  hipLaunchKernelGGL(hgs_k_mesh_scan1, dim3(gc), dim3(1024), 0, stream, G, grid);
+  hipLaunchKernelGGL(hgs_k_mesh_scan2, dim3(1), dim3(1024), 0, stream, G, grid);
+  hipLaunchKernelGGL(hgs_k_mesh_scan3, dim3(gc), dim3(1024), 0, stream, G, grid);
+  hipLaunchKernelGGL(hgs_k_mesh_bin, dim3(gf), dim3(256), 0, stream, G, grid, 1);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_mesh_query(int32_t P, const float* points, int32_t V, const float* vertices, int32_t F, const int32_t* faces,
+                   const void* grid, int32_t mode, float* dist, int32_t* face, float* uvw, void* stream_) {
+  if (P < 0 || V < 0 || F < 0 || (mode != HGS_MESH_UNSIGNED && mode != HGS_MESH_RAYSTAB)) return HGS_EINVAL;
+  if (P == 0) return HGS_OK;
+  if (F == 0 || !points || !dist || !face) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const unsigned gp = (unsigned)((P + 255) / 256);
+  if (grid) {
+    hipLaunchKernelGGL(hgs_k_mesh_query_grid, dim3(gp), dim3(256), 0, stream, (int)P, points, grid, (int)mode, dist, face, uvw);
+  } else {
+    if (!faces || (V > 0 && !vertices)) return HGS_EINVAL;
+    hipLaunchKernelGGL(hgs_k_mesh_query_brute, dim3(gp), dim3(256), 0, stream, (int)P, points, (int)V, vertices, (int)F,
+                       faces, (int)mode, dist, face, uvw);
+  }
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

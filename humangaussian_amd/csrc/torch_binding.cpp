@@ -891,6 +891,84 @@ py::dict device_state(int64_t dev) {
 
 }  // namespace
 
+// ---- closest point / signed distance to a triangle mesh (include/hgs_rast.h: hgs_mesh_*; the reference's cubvh) -----
+namespace {
+std::pair<Tensor, Tensor> mesh_inputs(const Tensor& vertices, const Tensor& faces, const c10::Device& dev) {
+  if (vertices.dim() != 2 || vertices.size(1) != 3) throw std::runtime_error("vertices must have dimensions (V, 3)");
+  if (faces.dim() != 2 || faces.size(1) != 3) throw std::runtime_error("faces must have dimensions (F, 3)");
+  if (faces.device() != dev) throw std::runtime_error("expected faces on " + dev.str() + ", got " + faces.device().str());
+  if (at::isFloatingType(faces.scalar_type())) throw std::runtime_error("faces must hold integer vertex indices");
+  if (vertices.size(0) > 0x7fffffffll / 3 || faces.size(0) > 0x7fffffffll / 48)
+    throw std::runtime_error("mesh too large");
+  return {f32c(vertices, dev, "vertices"), faces.to(at::kInt).contiguous()};
+}
+}  // namespace
+
+// Plan + build of the uniform grid: one host wait (the plan's header decides the grid's size).  Returns (grid bytes,
+// [dims x, y, z, ncells, num_refs]).  F == 0: an empty grid (queries of P > 0 points then fail).
+std::tuple<Tensor, std::vector<int64_t>> mesh_build(const Tensor& vertices, const Tensor& faces) {
+  at::NoGradGuard ng;
+  const c10::Device dev = vertices.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  const auto vf = mesh_inputs(vertices, faces, dev);
+  const Tensor &v = vf.first, &f = vf.second;
+  const int64_t V = v.size(0), F = f.size(0);
+  const auto byte_opts = at::TensorOptions().dtype(at::kByte).device(dev);
+  if (F == 0) return {at::empty({0}, byte_opts), {0, 0, 0, 0, 0}};
+  const int64_t lo = f.min().item<int64_t>(), hi = f.max().item<int64_t>();
+  if (lo < 0 || hi >= V)
+    throw std::runtime_error("faces index vertices outside [0, " + std::to_string(V) + "): min " + std::to_string(lo) +
+                             ", max " + std::to_string(hi));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  Tensor info_dev = at::empty({(int64_t)sizeof(hgs_mesh_grid_info)}, byte_opts);
+  auto* info_ptr = reinterpret_cast<hgs_mesh_grid_info*>(info_dev.data_ptr());
+  check_rc(hgs_mesh_grid_plan((int32_t)V, fptr(v), (int32_t)F, f.data_ptr<int32_t>(), info_ptr, stream), "hgs_mesh_grid_plan");
+  hgs_mesh_grid_info info;
+  if (hipMemcpyAsync(&info, info_ptr, sizeof(info), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    throw std::runtime_error("mesh_build: reading the grid plan failed");
+  const size_t bytes = hgs_mesh_grid_bytes(&info);
+  if (bytes == 0)
+    throw std::runtime_error("mesh_build: the grid plan is unusable (" + std::to_string(info.num_refs) +
+                             " face references; at most 2^31 - 1)");
+  Tensor grid = at::empty({(int64_t)bytes}, byte_opts);
+  check_rc(hgs_mesh_grid_build((int32_t)V, fptr(v), (int32_t)F, f.data_ptr<int32_t>(), &info, grid.data_ptr(), stream),
+           "hgs_mesh_grid_build");
+  return {grid, {info.dims[0], info.dims[1], info.dims[2], (int64_t)info.ncells, (int64_t)info.num_refs}};
+}
+
+// (dist [P] fp32, face [P] int32, uvw [P, 3] fp32 or undefined).  grid: mesh_build's, or None = brute force.
+std::tuple<Tensor, Tensor, c10::optional<Tensor>> mesh_query(const Tensor& points, const Tensor& vertices,
+                                                             const Tensor& faces, const c10::optional<Tensor>& grid,
+                                                             bool raystab, bool want_uvw) {
+  at::NoGradGuard ng;
+  const c10::Device dev = points.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  if (points.dim() != 2 || points.size(1) != 3) throw std::runtime_error("points must have dimensions (P, 3)");
+  if (points.size(0) > 0x7fffffffll / 3) throw std::runtime_error("too many points");
+  DeviceSwitch guard(dev.index());
+  const auto vf = mesh_inputs(vertices, faces, dev);
+  const Tensor &v = vf.first, &f = vf.second;
+  const Tensor pts = f32c(points, dev, "points");
+  const bool use_grid = grid.has_value() && grid->defined() && grid->numel() > 0;
+  if (use_grid && (grid->device() != dev || grid->scalar_type() != at::kByte))
+    throw std::runtime_error("grid must be the uint8 tensor mesh_build returned, on the points' device");
+  const int64_t P = pts.size(0);
+  const auto opts = at::TensorOptions().device(dev);
+  Tensor dist = at::empty({P}, opts.dtype(at::kFloat)), face = at::empty({P}, opts.dtype(at::kInt));
+  c10::optional<Tensor> uvw;
+  if (want_uvw) uvw = at::empty({P, 3}, opts.dtype(at::kFloat));
+  if (P > 0 && f.size(0) == 0) throw std::runtime_error("mesh query: the mesh has no faces");
+  check_rc(hgs_mesh_query((int32_t)P, fptr(pts), (int32_t)v.size(0), fptr(v), (int32_t)f.size(0),
+                          f.numel() ? f.data_ptr<int32_t>() : nullptr, use_grid ? grid->data_ptr() : nullptr,
+                          raystab ? HGS_MESH_RAYSTAB : HGS_MESH_UNSIGNED, dist.data_ptr<float>(), face.data_ptr<int32_t>(),
+                          want_uvw && P > 0 ? uvw->data_ptr<float>() : nullptr,
+                          c10::hip::getCurrentHIPStream(dev.index()).stream()),
+           "hgs_mesh_query");
+  return {dist, face, uvw};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch binding of libhgs_rast.so (include/hgs_rast.h): autograd node, capacity logic, the one host wait";
   m.def("rasterize", &rasterize, py::call_guard<py::gil_scoped_release>());
@@ -909,6 +987,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("densify_masks", &densify_masks, py::call_guard<py::gil_scoped_release>());
   m.def("compact_rows", &compact_rows, py::call_guard<py::gil_scoped_release>());
   m.def("reanchor", &reanchor, py::call_guard<py::gil_scoped_release>());
+  m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
+  m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
+        py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);
   m.def("abi_version", []() { return hgs_abi_version(); });

@@ -368,6 +368,51 @@ int hgs_gather_rows(int64_t n_out, int32_t row_floats, const int32_t* src_of_dst
 int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const int32_t* mapping_face,
                  const float* mapping_uvw, const float* mapping_dist, float* xyz, void* stream);
 
+/* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
+ * The per-avatar anchoring of /root/reference/animation.py:333-378:
+ *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
+ * vertices [V][3] fp32, faces [F][3] int32, points [P][3] fp32.  This definition is the contract (cubvh's sign test is
+ * modelled on instant-ngp's ray stab; its exact directions are not reproduced):
+ *   - face[i] = the face minimising the fp32 squared distance d2 from point i to the triangle, ties to the lowest index
+ *     ((d2, face) in lexicographic order).  Faces whose fp32 cross(v1 - v0, v2 - v0) is exactly zero (or not finite, or
+ *     with an index outside [0, V)) are skipped.  uvw[i] = barycentric weights of the closest point (Ericson's
+ *     region-based closest point on a triangle: closest = u v0 + v v1 + w v2, each >= 0, sum 1), dist[i] = sqrt(d2).
+ *   - a point with a non-finite coordinate (or no face to measure against) gets face -1, dist NaN, uvw 0.
+ *   - HGS_MESH_RAYSTAB: rays from the point along +-d_i, the 32 Fibonacci-lattice directions z_i = 1 - (2i + 1) / 32,
+ *     theta_i = 2 pi frac(0.6180339887 i + 0.1234).  The point is INSIDE iff all 64 rays hit a non-skipped face at t > 0
+ *     (watertight test of Woop, Benthin and Wald 2013: a ray through a shared edge or vertex does not slip between the
+ *     triangles); then dist is negated (positive = outside for an outward-wound mesh).  HGS_MESH_UNSIGNED: no sign.
+ * The grid path and the brute force (grid == NULL) return bit-identical dist, face and uvw.
+ *
+ * The grid's size depends on the data and the library does not allocate or synchronise, so it is built in two steps:
+ *   1. hgs_mesh_grid_plan writes the box, the grid dimensions and the number of (face, cell) references into `info`
+ *      (DEVICE, one hgs_mesh_grid_info);
+ *   2. the caller copies `info` to the host once per mesh, allocates hgs_mesh_grid_bytes(&info_host) bytes (0: the plan
+ *      is unusable - more than 2^31 - 1 references, or not a plan) and calls hgs_mesh_grid_build with the same
+ *      vertices and faces.  The grid holds its own copy of the triangles; queries reuse it.
+ * hgs_mesh_query: grid = a built grid (then vertices / faces are not read) or NULL (brute force over all faces: O(P F),
+ * and O(64 P F) for the sign).  uvw [P][3] may be NULL.  F == 0 with P > 0 is HGS_EINVAL.
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_MESH_UNSIGNED 0
+#define HGS_MESH_RAYSTAB 1
+typedef struct hgs_mesh_grid_info {
+  uint32_t bmin[3], bmax[3];  /* order-preserving integer images of the box of the finite vertices (the plan's own use) */
+  int32_t dims[3];            /* cells per axis                                                                      */
+  uint32_t ncells;            /* dims[0] * dims[1] * dims[2]                                                         */
+  float origin[3];            /* low corner of the box                                                               */
+  float cell;                 /* cell edge                                                                           */
+  int32_t num_faces;          /* F of the plan                                                                       */
+  int32_t reserved0;
+  uint64_t num_refs;          /* (face, cell) references: every non-skipped face in every cell of its bounding box   */
+} hgs_mesh_grid_info;
+int hgs_mesh_grid_plan(int32_t V, const float* vertices, int32_t F, const int32_t* faces, hgs_mesh_grid_info* info,
+                       void* stream);
+size_t hgs_mesh_grid_bytes(const hgs_mesh_grid_info* info_host);
+int hgs_mesh_grid_build(int32_t V, const float* vertices, int32_t F, const int32_t* faces,
+                        const hgs_mesh_grid_info* info_host, void* grid, void* stream);
+int hgs_mesh_query(int32_t P, const float* points, int32_t V, const float* vertices, int32_t F, const int32_t* faces,
+                   const void* grid, int32_t mode, float* dist, int32_t* face, float* uvw, void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
