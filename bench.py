@@ -27,13 +27,21 @@ frame k on rank k mod N; N > 1: one image all-gather per step, in flight under t
 `--dump-outputs DIR` writes what the last of the K timed steps handed its caller (images, radii, gradients; the last frame
 with --forward-only) as DIR/<name>.npy (`dump_outputs`); the inputs are seeded, so two builds compare output for output.
 
-Extra objects on the JSON line:
-  roofline      dominant kernel, timed live with HIP events recorded by the library on its launch stream
-  cpu_baseline  the PyTorch CPU oracle, full fwd+bwd of the same view on the host cores (rank 0, N=1)
-  extra         further measurements of the same path, same rules (rank 0, N=1): the 8-view BATCHED call
+A plain run does only what the headline needs: set up, the un-timed init steps, W warm-up and K timed steps, the dump,
+the JSON line (N > 1 with --collective auto: also the per-mode collective timing that picks the mode of the timed steps).
+`--full` adds everything else, after the timed steps (N > 1: the collective measurements before them, where they were):
+  host          host/GPU balance of the headline step (50 more steps, binding timers)
+  stage_us      per-kernel-stage times, HIP events recorded by the library on its launch stream (20 more steps)
+  roofline      the dominant stage priced against HBM from those stage times
+  cpu_baseline  the PyTorch CPU oracle, full fwd+bwd of the same view on the host cores (rank 0, N=1; --no-cpu-baseline)
+  extra         further measurements of the same path, same rules (rank 0, N=1; --no-extra): the 8-view BATCHED call
                 (one launch set for the 8 views of a training step), the `init`-state
                 cloud, configs[3] (500k Gaussians, SH degree 3), forward-only (configs[4] shape), the 300-frame
                 animation loop, the drop-in render() on raw parameters (un-fused and with fuse_activations)
+  collective    N > 1: both collective modes timed whatever --collective says, and `exposed`: the step with and without
+                its collectives for 1 and 2 views per rank; --forward-only: the frame loop without the image gather
+A plain run writes null for host, stage_us, roofline, cpu_baseline, extra and collective.exposed, and for
+collective.timings unless --collective auto.
 """
 import argparse
 import json
@@ -125,8 +133,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (batched, init, config 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: host/GPU balance, per-kernel stage times and "
+                         "roofline, the CPU baseline, the extra measurements, (N > 1) the exposed cost of the collectives")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra measurements (batched, init, config 4)")
     ap.add_argument("--points", type=int, default=P_POINTS)
     ap.add_argument("--sh-degree", type=int, default=SH_DEGREE)
     ap.add_argument("--variant", default="mid", choices=["mid", "init"])
@@ -501,7 +513,7 @@ def main():
         frames = args.steps * world
         line = None
         without = None
-        if world > 1:
+        if world > 1 and args.full:
             wl2 = AnimationWorkload(P, gather=False)
             without = wl2.timed(args.steps, args.warmup, init_steps=min(args.init_steps, 20))
         if rank == 0:
@@ -530,7 +542,8 @@ def main():
     main_wl = Workload(P, sh_degree, args.variant, args.views, args.forward_only, first_view=rank * args.views, seq_views=VPR)
 
     # ---------------- N > 1: what the collective of a step costs, per mode (OUTSIDE the timed region);
-    # --collective auto then runs the timed steps with the faster mode (every rank takes the same decision)
+    # --collective auto then runs the timed steps with the faster mode (every rank takes the same decision).
+    # A plain run times the modes only when it has to choose; --full always, and adds the exposed-cost runs
     collective = None
     if world > 1:
         # (no pack pass since ABI v15: the backward's last kernel writes the pack; the timed part is the collective + the
@@ -539,7 +552,7 @@ def main():
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         nrep = 20
         res = {}
-        for mode in vp.COLLECTIVE_MODES:
+        for mode in (vp.COLLECTIVE_MODES if args.collective == "auto" or args.full else ()):
             acc = 0.0
             for it in range(nrep + 5):
                 fence()
@@ -560,14 +573,14 @@ def main():
         # kernel of the step) and for two (round 0's all-gather runs under round 1's render)
         exposed = {}
         ksteps = max(10, args.steps // 10)
-        for vpr in (1, 2):
+        for vpr in ((1, 2) if args.full else ()):
             t_with = Workload(P, sh_degree, args.variant, 1, False, 0, seq_views=vpr).timed(ksteps, 3, init_steps=min(args.init_steps, 20))
             t_wo = Workload(P, sh_degree, args.variant, 1, False, 0, seq_views=vpr, collectives=False).timed(ksteps, 3, init_steps=min(args.init_steps, 20))
             exposed[f"views_per_rank_{vpr}"] = {"step_us_with": t_with / ksteps * 1e6, "step_us_without": t_wo / ksteps * 1e6,
                                                 "exposed_collective_us": (t_with - t_wo) / ksteps * 1e6}
         collective = {"mode_used": collective_mode[0] if VPR == 1 else "allgather per round, pipelined", "requested": args.collective,
-                      "backend": backend, "views_per_rank": VPR, "timings": res, "exposed": exposed,
-                      "exposed_collective_us": exposed[f"views_per_rank_{min(VPR, 2)}"]["exposed_collective_us"],
+                      "backend": backend, "views_per_rank": VPR, "timings": res or None, "exposed": exposed or None,
+                      "exposed_collective_us": exposed[f"views_per_rank_{min(VPR, 2)}"]["exposed_collective_us"] if exposed else None,
                       "bytes_per_rank_pack": int(pack.numel() * 4),
                       "note": "allgather = ONE all_gather_into_tensor of the per-rank gradient packs + rank-ordered local "
                               "reduction; scatter = all_to_all of row shards + the same local reduction + one all-gather of "
@@ -582,65 +595,88 @@ def main():
     ms = elapsed / args.steps * 1e3
     M = main_wl.M
 
-    # ---------------- host/GPU balance (outside the timed region): time the host spends blocked
-    # in the one event wait per forward.  wait ~ 0 means the loop is host-bound.
-    nhost = 50
-    st0 = _rast._state(dev)
-    w0 = st0.wait_ns
-    th = time.perf_counter()
-    for _ in range(nhost):
-        main_wl.step()
-    torch.cuda.synchronize()
-    th = time.perf_counter() - th
-    st_now = _rast._state(dev)
-    hb = {k: round((st_now.host_ns[k] - st0.host_ns[k]) / nhost * 1e-3, 1) for k in st_now.host_ns}
-    host_info = {"step_us": round(th / nhost * 1e6, 1),
-                 "event_wait_us": round((st_now.wait_ns - w0) / nhost * 1e-3, 1),
-                 # inside the binding (us per step): forward = pre (checks, allocations) + launch (hgs_forward: 5 kernel
-                 # launches) + shadow (autograd state, gradient tensors) + wait (status poll) + rest; backward likewise;
-                 # step_us - fwd_total - bwd_total = Python, the autograd engine and its thread hand-off
-                 "binding_us": hb,
-                 "forward_retries_total": int(st_now.retries), "forward_calls_total": int(st_now.calls)}
-
-    # ---------------- host/GPU balance etc. follow below
-    # ---------------- per-kernel timing (outside the timed region; library-recorded events)
-    stage_us = main_wl.stage_times()
     R = int(_rast._state(dev).max_R)
     npix, T = RES * RES, (RES // 16) ** 2
-    B = args.views
-    # upstream's stages: the blend backward (B1) is render_bwd + pair_reduce here, priced together
-    merged_us = {name: sum(stage_us[k] for k in parts) for name, parts in ROOFLINE_STAGES.items()
-                 if not (args.forward_only and any(k in BWD_STAGES for k in parts))}
-    merged_bytes = {name: sum(algorithmic_bytes(k, P, M, R, npix, T, B) for k in ROOFLINE_STAGES[name]) for name in merged_us}
-    merged_bytes["blend_bwd(render_bwd+pair_reduce)"] = 84 * R + 28 * npix * B       # (B1 = 84 R + 28 N_pix)
-    dom = max(merged_us, key=merged_us.get)
-    dom_bytes = merged_bytes[dom]
-    achieved = dom_bytes / (merged_us[dom] * 1e-6) / 1e9
-    # HBM-side bytes of the dominant kernel from the committed PMC passes (tools/gpu_round.sh pmc), with the commit
-    # they were taken at: the two must be read together (the counters cannot be collected inside this process)
-    traffic, traffic_commit = None, None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    counters = None
-    if os.path.exists(tpath) and B == 1:
-        try:
-            tj = json.load(open(tpath))
-            parts = [tj.get(k) for k in ROOFLINE_STAGES[dom]]
-            traffic, traffic_commit = (sum(parts) if all(x is not None for x in parts) else None), tj.get("_commit")
-        except Exception:
-            traffic = None
-    cpath = os.path.join(ROOT, "profiles", "sq_counters.json")
-    if os.path.exists(cpath) and B == 1:
-        try:
-            counters = json.load(open(cpath))         # committed SQ-counter passes (tools/sq_pass.sh) -> VALU busy per blend kernel
-        except Exception:
-            counters = None
-    path_bytes = path_bytes_survey(P, M, R, npix, T, B, args.forward_only)
-    gpu_us = sum(stage_us.values())
-    blend_us = stage_us["render_fwd"] + (0.0 if args.forward_only else stage_us.get("render_bwd", 0.0) + stage_us.get("pair_reduce", 0.0))
+    host_info = stage_us = roofline = None
+    if args.full:
+        # ---------------- host/GPU balance (outside the timed region): time the host spends blocked
+        # in the one event wait per forward.  wait ~ 0 means the loop is host-bound.
+        nhost = 50
+        st0 = _rast._state(dev)
+        w0 = st0.wait_ns
+        th = time.perf_counter()
+        for _ in range(nhost):
+            main_wl.step()
+        torch.cuda.synchronize()
+        th = time.perf_counter() - th
+        st_now = _rast._state(dev)
+        hb = {k: round((st_now.host_ns[k] - st0.host_ns[k]) / nhost * 1e-3, 1) for k in st_now.host_ns}
+        host_info = {"step_us": round(th / nhost * 1e6, 1),
+                     "event_wait_us": round((st_now.wait_ns - w0) / nhost * 1e-3, 1),
+                     # inside the binding (us per step): forward = pre (checks, allocations) + launch (hgs_forward: 5 kernel
+                     # launches) + shadow (autograd state, gradient tensors) + wait (status poll) + rest; backward likewise;
+                     # step_us - fwd_total - bwd_total = Python, the autograd engine and its thread hand-off
+                     "binding_us": hb,
+                     "forward_retries_total": int(st_now.retries), "forward_calls_total": int(st_now.calls)}
 
-    # ---------------- extra measurements of the same path (rank 0, N=1 only; same timing rules)
+        # ---------------- per-kernel timing (outside the timed region; library-recorded events)
+        stage_us = main_wl.stage_times()
+        B = args.views
+        # upstream's stages: the blend backward (B1) is render_bwd + pair_reduce here, priced together
+        merged_us = {name: sum(stage_us[k] for k in parts) for name, parts in ROOFLINE_STAGES.items()
+                     if not (args.forward_only and any(k in BWD_STAGES for k in parts))}
+        merged_bytes = {name: sum(algorithmic_bytes(k, P, M, R, npix, T, B) for k in ROOFLINE_STAGES[name]) for name in merged_us}
+        merged_bytes["blend_bwd(render_bwd+pair_reduce)"] = 84 * R + 28 * npix * B       # (B1 = 84 R + 28 N_pix)
+        dom = max(merged_us, key=merged_us.get)
+        dom_bytes = merged_bytes[dom]
+        achieved = dom_bytes / (merged_us[dom] * 1e-6) / 1e9
+        # HBM-side bytes of the dominant kernel from the committed PMC passes (tools/gpu_round.sh pmc), with the commit
+        # they were taken at: the two must be read together (the counters cannot be collected inside this process)
+        traffic, traffic_commit = None, None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        counters = None
+        if os.path.exists(tpath) and B == 1:
+            try:
+                tj = json.load(open(tpath))
+                parts = [tj.get(k) for k in ROOFLINE_STAGES[dom]]
+                traffic, traffic_commit = (sum(parts) if all(x is not None for x in parts) else None), tj.get("_commit")
+            except Exception:
+                traffic = None
+        cpath = os.path.join(ROOT, "profiles", "sq_counters.json")
+        if os.path.exists(cpath) and B == 1:
+            try:
+                counters = json.load(open(cpath))         # committed SQ-counter passes (tools/sq_pass.sh) -> VALU busy per blend kernel
+            except Exception:
+                counters = None
+        path_bytes = path_bytes_survey(P, M, R, npix, T, B, args.forward_only)
+        gpu_us = sum(stage_us.values())
+        blend_us = stage_us["render_fwd"] + (0.0 if args.forward_only else stage_us.get("render_bwd", 0.0) + stage_us.get("pair_reduce", 0.0))
+        flops_pair = 25 if args.forward_only else 105
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": {"file": "profiles/pmc_traffic.json", "commit": traffic_commit},
+                    "algorithmic_bytes": dom_bytes, "avg_us": merged_us[dom],
+                    "note": "stage = upstream's stage (B1 = render_bwd + pair_reduce); blend kernels are VALU / LDS / "
+                            "MFMA-issue-bound (the backward's pixel sums run on fp32 MFMA); HBM fraction reported as "
+                            "BASELINE.json asks",
+                    # the whole path: SURVEY.md 8(d)'s byte formula over the WALL time of a step (not the event sum)
+                    "path": {"algorithmic_bytes": path_bytes, "ms_per_step": ms, "stage_event_us_sum": gpu_us,
+                             "achieved": path_bytes / (ms * 1e-3) / 1e9 / max(1, VPR),
+                             "frac": path_bytes / (ms * 1e-3) / 1e9 / max(1, VPR) / HBM_PEAK_GBS},
+                    # how much faster than UPSTREAM'S BRUTE FORCE (256 pixel-Gaussian pairs per entry, ~25 flop forward
+                    # + ~80 backward) the blend stages run, expressed against the fp32 vector peak.  NOT a utilisation:
+                    # the kernels evaluate ~57 lane slots per entry, not 256 (see valu_busy for what the pipes do)
+                    "brute_force_equivalent": {"flops": 256.0 * R * flops_pair,
+                                               "tflops": 256.0 * R * flops_pair / (blend_us * 1e-6) / 1e12,
+                                               "of_fp32_vector_peak_157.3": 256.0 * R * flops_pair / (blend_us * 1e-6) / 1e12 / 157.3,
+                                               "kernels": "render_fwd + render_bwd + pair_reduce"},
+                    # counter-derived (committed profiles/sq_counters.json: SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x
+                    # 2.4 GHz x kernel time)); live lanes: 34 contributing pixels per 57 evaluated lane slots per entry
+                    "valu_busy": (counters or {}).get("valu_busy"), "live_lane_fraction": 34.0 / 57.0}
+
+    # ---------------- --full: extra measurements of the same path (rank 0, N=1 only; same timing rules)
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.forward_only and args.views == 1 \
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.forward_only and args.views == 1 \
             and P == P_POINTS and sh_degree == SH_DEGREE and args.variant == "mid":
         extra = {}
 
@@ -706,10 +742,10 @@ def main():
         measure("config4_500k_sh3", Workload(500_000, 3, "mid", 1, False, 0), max(20, args.steps // 6), max(5, args.warmup // 5),
                 500_000, "configs[3]: 500k Gaussians, SH degree 3, one 1024^2 view, fwd+bwd", roof=("cfg3_", 500_000, 16, 1))
 
-    # ---------------- CPU baseline: the PyTorch oracle on the host cores (rank 0, N=1): the FULL
+    # ---------------- --full: CPU baseline, the PyTorch oracle on the host cores (rank 0, N=1): the FULL
     # forward + backward of the same view (every tile), 1 warm-up + median of 3.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.views == 1 and not args.forward_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.views == 1 and not args.forward_only:
         import oracle
         cloud, cam, rs = main_wl.cloud, main_wl.cams[0], main_wl.rs[0]
         st = oracle.OracleSettings(RES, RES, rs.tanfovx, rs.tanfovy, torch.zeros(3), 1.0, cam.world_view_transform,
@@ -739,7 +775,6 @@ def main():
                          f"torch {torch.__version__}"}
 
     if rank == 0:
-        flops_pair = 25 if args.forward_only else 105
         line = {
             "metric": "rasterize fwd+bwd Gaussians/sec @1024^2, 100k pts" if not args.forward_only
             else "rasterize fwd-only Gaussians/sec @1024^2 (extra measurement)",
@@ -767,27 +802,7 @@ def main():
                        "views_per_step": world * args.views * VPR, "views_per_rank_sequential": VPR, "num_rendered_R": int(R),
                        "host_mode": "sync (one host wait per forward for the device-side status, as upstream)",
                        "parallelism": f"view-parallel x{world}" + (f", collective {collective_mode[0]}" if world > 1 else "")},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": {"file": "profiles/pmc_traffic.json", "commit": traffic_commit},
-                         "algorithmic_bytes": dom_bytes, "avg_us": merged_us[dom],
-                         "note": "stage = upstream's stage (B1 = render_bwd + pair_reduce); blend kernels are VALU / LDS / "
-                                 "MFMA-issue-bound (the backward's pixel sums run on fp32 MFMA); HBM fraction reported as "
-                                 "BASELINE.json asks",
-                         # the whole path: SURVEY.md 8(d)'s byte formula over the WALL time of a step (not the event sum)
-                         "path": {"algorithmic_bytes": path_bytes, "ms_per_step": ms, "stage_event_us_sum": gpu_us,
-                                  "achieved": path_bytes / (ms * 1e-3) / 1e9 / max(1, VPR),
-                                  "frac": path_bytes / (ms * 1e-3) / 1e9 / max(1, VPR) / HBM_PEAK_GBS},
-                         # how much faster than UPSTREAM'S BRUTE FORCE (256 pixel-Gaussian pairs per entry, ~25 flop forward
-                         # + ~80 backward) the blend stages run, expressed against the fp32 vector peak.  NOT a utilisation:
-                         # the kernels evaluate ~57 lane slots per entry, not 256 (see valu_busy for what the pipes do)
-                         "brute_force_equivalent": {"flops": 256.0 * R * flops_pair,
-                                                    "tflops": 256.0 * R * flops_pair / (blend_us * 1e-6) / 1e12,
-                                                    "of_fp32_vector_peak_157.3": 256.0 * R * flops_pair / (blend_us * 1e-6) / 1e12 / 157.3,
-                                                    "kernels": "render_fwd + render_bwd + pair_reduce"},
-                         # counter-derived (committed profiles/sq_counters.json: SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x
-                         # 2.4 GHz x kernel time)); live lanes: 34 contributing pixels per 57 evaluated lane slots per entry
-                         "valu_busy": (counters or {}).get("valu_busy"), "live_lane_fraction": 34.0 / 57.0},
+            "roofline": roofline,
             "stage_us": stage_us,
             "host": host_info,
             "collective": collective,

@@ -19,7 +19,7 @@ def _run_bench(extra):
     env = dict(os.environ, HGS_DIST_BACKEND="gloo", HGS_BENCH_SHARE_DEVICE="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--init-steps", "6", "--points", "20000", "--no-cpu-baseline", "--no-extra"] + extra
+           "--init-steps", "6", "--points", "20000", "--full", "--no-cpu-baseline", "--no-extra"] + extra
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

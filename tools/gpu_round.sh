@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/gpu_round.sh MODE ...   - what a gpurun call runs on the GPU box (the repo root is taken from this file's place).
 #   tests                 the whole `-m gpu` suite + smoke()                                    -> gpurun_out/suite_*.log, parity_fullsize.json
-#   suite                 tests + the default bench line                                        -> ... + bench_default.json
+#   suite                 tests + the --full bench line                                         -> ... + bench_default.json
 #   ab NAME ...           short benches (AB_CONFIGS, default "1v 8v cfg3": one view, 8 views batched, configs[3]) of the in-tree
 #                         build and of every variants/NAME/libhgs_rast.so (tools/mkvariant.sh; LD_PRELOAD) -> gpurun_out/ab_*.json
 #   quick                 parity + batch suites only (fast gate for a kernel change)
@@ -17,7 +17,7 @@ TAG=r06
 
 bench_line() {  # name, preload, extra bench args...
   local N=$1 PRE=$2; shift 2
-  (cd $R && LD_PRELOAD=$PRE timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 100 --warmup 10 "$@" 2>$O/ab_$N.err > $O/ab_$N.json)
+  (cd $R && LD_PRELOAD=$PRE timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 100 --warmup 10 "$@" 2>$O/ab_$N.err > $O/ab_$N.json)
   python - "$N" "$O/ab_$N.json" <<'PY'
 import json, sys
 n, p = sys.argv[1], sys.argv[2]
@@ -38,7 +38,7 @@ mode_tests() {
 mode_suite() {
   mode_tests
   cd $R
-  timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
+  timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
 }
 
 mode_quick() {
