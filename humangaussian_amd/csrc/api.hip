@@ -58,8 +58,10 @@ inline int cu_count(hipStream_t stream) {
   return cus;
 }
 #define HGS_CHUNK_ROWS_MIN_VIEWS 3     // calls with at least this many views keep the backward's pair rows chunk-cell-major (binning.hip::hgs_put_pair)
+#ifndef HGS_PRE_BWD_VPAR_MIN_VIEWS     // (a test build sets it above HGS_MAX_VIEWS: every multi-view call then takes the loop form)
 #define HGS_PRE_BWD_VPAR_MIN_VIEWS 2   // calls with at least this many views run the per-Gaussian backward with one thread per
                                        // (Gaussian, view); fewer: one thread per Gaussian
+#endif
 constexpr size_t ALIGN = 256;
 constexpr size_t HGS_LDS_BINS_MAX = 16384;   // T*4 bytes of LDS <= 64 KB
 #define HGS_BIN_WGS_PER_VIEW_MAX 512   // (256 until round 5: at 500k Gaussians a workgroup then walked 8 chunks one after the other -

@@ -494,6 +494,23 @@ namespace {
 // which carries sums across a loop: the 8-view backward was a latency chain of 1.5 waves per SIMD.
 // AA: the antialiasing filter's chain rule (HGS_ANTIALIAS); 0: off, 1: on, 2: decided at run time from v.act (the one
 // form whose compile-time copy would not fit its registers: the loop over the views at SH degree 3).
+//
+// Which kernel serves which call (api.hip, the switch behind HGS_LAUNCH_PRE_BWD; D = the active SH degree, 0 with
+// colors_precomp whatever the settings say; `_aa` = the filter's copy):
+//
+//   views B   D = 0         D = 1         D = 2         D = 3
+//   1         s0 / s0_aa    s1 / s1_aa    s2 / s2_aa    s3 / s3_aa     (D >= 1, 4 <= M <= 16, six tensors: SH blocks of full
+//                                                                       256-chunks through LDS; else 16 B vectors when
+//                                                                       3 M % 4 == 0 and M <= 16; else scalars)
+//   2 .. 8    p0 / p0_aa    p1 / p1_aa    p2 / p2_aa    p3 / p3_aa     (exchange buffer (23 + 3 (D+1)^2) * 64 B floats of LDS;
+//   9 .. 16   p0 / p0_aa    p1 / p1_aa    d2 / d2_aa    d3 / d3 + bit    above 64 KB - from 10 views at D = 0, 8 at D = 1,
+//                                                                        6 at D = 2, 4 at D = 3 - the dynamic-LDS limit is
+//                                                                        raised first)
+//
+// d0, d1, d0_aa, d1_aa serve only where that raise is refused (then also d2 / d3 for the calls above 64 KB) or
+// in a build with HGS_PRE_BWD_VPAR_MIN_VIEWS above HGS_MAX_VIEWS (api.hip), which sends every multi-view call through
+// the loop: tests/test_gpu_pre_bwd_matrix.py builds that twin to run them and to compare the two forms bit for bit.
+// 24 targets, 23 kernels: d3 serves the filter through v.act.
 template <int DEG, int MODE, int AA>
 __device__ __forceinline__ void preprocess_bwd_body(
     const View& v, const Layout& L, const hgs_status* __restrict__ status,
