@@ -98,6 +98,14 @@ EXPORTS = {
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_query": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgs_field_plan_bytes": (c_size_t, [c_int32, c_int32]),
+    "hgs_field_plan": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p,
+                                                               c_void_p]),
+    "hgs_field_list_bytes": (c_size_t, [c_void_p]),
+    "hgs_field_eval": (ctypes.c_int, [c_void_p] * 7),
+    "hgs_mc_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "hgs_mc_count": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "hgs_mc_emit": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float] + [c_void_p] * 5),
 }
 
 

@@ -23,6 +23,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "render_fwd.hip"
 #include "knn.hip"
 #include "mesh.hip"
+#include "fields.hip"
 #include "bookkeeping.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
@@ -1020,6 +1021,171 @@ int hgs_mesh_query(int32_t P, const float* points, int32_t V, const float* verti
     hipLaunchKernelGGL(hgs_k_mesh_query_brute, dim3(gp), dim3(256), 0, stream, (int)P, points, (int)V, vertices, (int)F,
                        faces, (int)mode, dist, face, uvw);
   }
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+namespace {
+struct FieldPlanCarve { size_t rec, reach, bounds, counts, total; };
+FieldPlanCarve carve_field_plan(int32_t P, int32_t nb) {
+  FieldPlanCarve c;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  c.rec = take((size_t)P * HGS_FIELD_REC_FLOATS * 4);
+  c.reach = take((size_t)P * 4);
+  c.bounds = take(2 * HGS_FIELD_MAX_BLOCKS * 4);
+  c.counts = take((size_t)nb * nb * nb * 4);
+  c.total = off;
+  return c;
+}
+struct FieldListCarve { size_t start, order, refs, total; };
+FieldListCarve carve_field_lists(int32_t nb, uint64_t nrefs) {
+  FieldListCarve c;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  const size_t nblocks = (size_t)nb * nb * nb;
+  c.start = take((nblocks + 1) * 4);
+  c.order = take(nblocks * 4);
+  c.refs = take((size_t)nrefs * 4);
+  c.total = off;
+  return c;
+}
+bool field_dims_ok(int32_t P, int32_t R, int32_t nb) {
+  return P >= 0 && nb >= 1 && nb <= HGS_FIELD_MAX_BLOCKS && R >= nb && R <= HGS_FIELD_MAX_RES && R % nb == 0 &&
+         R / nb <= HGS_FIELD_MAX_SPLIT;
+}
+bool field_info_ok(const hgs_field_info* in) {
+  return in && field_dims_ok(in->num_gaussians, in->resolution, in->num_blocks) && in->num_refs <= 0x7fffffffull &&
+         in->num_kept <= (uint32_t)in->num_gaussians;
+}
+FieldPlanPtrs field_plan_ptrs(const FieldPlanCarve& c, void* plan) {
+  char* b = static_cast<char*>(plan);
+  FieldPlanPtrs p;
+  p.rec = reinterpret_cast<float2*>(b + c.rec);
+  p.reach = reinterpret_cast<uint32_t*>(b + c.reach);
+  p.bounds = reinterpret_cast<float*>(b + c.bounds);
+  p.counts = reinterpret_cast<uint32_t*>(b + c.counts);
+  return p;
+}
+struct McCarve { size_t offs, bsum, mask, total; };
+bool mc_dims_ok(int32_t X, int32_t Y, int32_t Z) {
+  if (X < 1 || Y < 1 || Z < 1) return false;
+  const unsigned long long xy = (unsigned long long)X * (unsigned long long)Y;      // < 2^62: cannot wrap
+  return xy <= (1ull << 28) && xy * (unsigned long long)Z <= (1ull << 28);
+}
+McCarve carve_mc(size_t N) {
+  McCarve c;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  c.offs = take((N + 1) * 8);
+  c.bsum = take(((N + 1023) / 1024 + 1) * 8);
+  c.mask = take(N);
+  c.total = off;
+  return c;
+}
+McPtrs mc_ptrs(const McCarve& c, void* scratch) {
+  char* b = static_cast<char*>(scratch);
+  McPtrs p;
+  p.offs = reinterpret_cast<uint2*>(b + c.offs);
+  p.bsum = reinterpret_cast<uint2*>(b + c.bsum);
+  p.mask = reinterpret_cast<uint8_t*>(b + c.mask);
+  return p;
+}
+}  // namespace
+
+size_t hgs_field_plan_bytes(int32_t P, int32_t num_blocks) {
+  if (P < 0 || num_blocks < 1 || num_blocks > HGS_FIELD_MAX_BLOCKS) return 0;
+  return carve_field_plan(P, num_blocks).total;
+}
+
+int hgs_field_plan(int32_t P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
+                   int32_t resolution, int32_t num_blocks, const float* axis, float grow, void* plan,
+                   hgs_field_info* info, void* stream_) {
+  if (!field_dims_ok(P, resolution, num_blocks) || !axis || !plan || !info || !(grow >= 0.0f)) return HGS_EINVAL;
+  if (P > 0 && (!xyz || !opacity || !scaling || !rotation)) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const FieldPlanCarve c = carve_field_plan(P, num_blocks);
+  const FieldPlanPtrs pp = field_plan_ptrs(c, plan);
+  const FieldDims D = {P, resolution, num_blocks, resolution / num_blocks};
+  const uint32_t nblocks = (uint32_t)(num_blocks * num_blocks * num_blocks);
+  hipError_t e = hipMemsetAsync(info, 0, sizeof(hgs_field_info), stream);
+  if (e == hipSuccess) e = hipMemsetAsync(&info->bmin[0], 0xff, 12, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(pp.counts, 0, (size_t)nblocks * 4, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  const unsigned gp = (unsigned)((P + 255) / 256);
+  if (P > 0) hipLaunchKernelGGL(hgs_k_field_bbox, dim3(gp), dim3(256), 0, stream, (int)P, xyz, opacity, info);
+  hipLaunchKernelGGL(hgs_k_field_setup, dim3(1), dim3(64), 0, stream, D, axis, grow, pp, info);
+  if (P > 0) {
+    hipLaunchKernelGGL(hgs_k_field_gauss, dim3(gp), dim3(256), 0, stream, D, xyz, opacity, scaling, rotation, pp, info);
+    hipLaunchKernelGGL(hgs_k_field_lists, dim3((nblocks + 3u) / 4u), dim3(256), 0, stream, D, pp, FieldListPtrs{nullptr, nullptr, nullptr}, 0, info);
+  }
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+size_t hgs_field_list_bytes(const hgs_field_info* info_host) {
+  if (!field_info_ok(info_host)) return 0;
+  return carve_field_lists(info_host->num_blocks, info_host->num_refs).total;
+}
+
+int hgs_field_eval(const hgs_field_info* info_host, const float* axis, const void* plan, void* lists, float* occ,
+                   int32_t* block_counts, void* stream_) {
+  if (!field_info_ok(info_host) || !axis || !plan || !lists || !occ) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hgs_field_info& in = *info_host;
+  const FieldDims D = {in.num_gaussians, in.resolution, in.num_blocks, in.resolution / in.num_blocks};
+  const FieldPlanPtrs pp = field_plan_ptrs(carve_field_plan(D.P, D.nb), const_cast<void*>(plan));
+  const FieldListCarve lc = carve_field_lists(D.nb, in.num_refs);
+  char* lb = static_cast<char*>(lists);
+  const FieldListPtrs lp = {reinterpret_cast<uint32_t*>(lb + lc.start), reinterpret_cast<uint32_t*>(lb + lc.order),
+                            reinterpret_cast<uint32_t*>(lb + lc.refs)};
+  const uint32_t nblocks = (uint32_t)(D.nb * D.nb * D.nb);
+  hipLaunchKernelGGL(hgs_k_field_order, dim3(1), dim3(1024), 0, stream, D, pp, lp);
+  if (in.num_refs > 0)
+    hipLaunchKernelGGL(hgs_k_field_lists, dim3((nblocks + 3u) / 4u), dim3(256), 0, stream, D, pp, lp, 1, (hgs_field_info*)nullptr);
+  const int items = ((D.split + 1) / 2) * D.split * D.split;
+  const int threads = items <= 64 ? 64 : 256;
+  const int slabs = (items + threads - 1) / threads;
+  hipLaunchKernelGGL(hgs_k_field_eval, dim3(nblocks * (unsigned)slabs), dim3(threads), 0, stream, D, axis, pp, lp, slabs, occ);
+  HGS_LAUNCH_CHECK();
+  if (block_counts) {
+    const hipError_t e = hipMemcpyAsync(block_counts, pp.counts, (size_t)nblocks * 4, hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return hip_rc(e);
+  }
+  return HGS_OK;
+}
+
+size_t hgs_mc_scratch_bytes(int32_t X, int32_t Y, int32_t Z) {
+  if (!mc_dims_ok(X, Y, Z)) return 0;
+  return carve_mc((size_t)X * Y * Z).total;
+}
+
+int hgs_mc_count(const float* field, int32_t X, int32_t Y, int32_t Z, float threshold, void* scratch, hgs_mc_info* info,
+                 void* stream_) {
+  if (!mc_dims_ok(X, Y, Z) || !field || !scratch || !info) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const McDims D = {X, Y, Z, (uint32_t)((size_t)X * Y * Z)};
+  const McPtrs p = mc_ptrs(carve_mc(D.N), scratch);
+  const unsigned g1k = (D.N + 1023u) / 1024u;
+  hipLaunchKernelGGL(hgs_k_mc_count, dim3((D.N + 255u) / 256u), dim3(256), 0, stream, D, field, threshold, p);
+  hipLaunchKernelGGL(hgs_k_mc_scan1, dim3(g1k), dim3(1024), 0, stream, D, p);
+  hipLaunchKernelGGL(hgs_k_mc_scan2, dim3(1), dim3(1024), 0, stream, D, p, info);
+  hipLaunchKernelGGL(hgs_k_mc_scan3, dim3(g1k), dim3(1024), 0, stream, D, p);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_mc_emit(const float* field, int32_t X, int32_t Y, int32_t Z, float threshold, const void* scratch,
+                const hgs_mc_info* info_host, float* vertices, int32_t* triangles, void* stream_) {
+  if (!mc_dims_ok(X, Y, Z) || !field || !scratch || !info_host) return HGS_EINVAL;
+  const uint32_t nv = info_host->num_vertices, nt = info_host->num_triangles;
+  const McDims D = {X, Y, Z, (uint32_t)((size_t)X * Y * Z)};
+  if (nv > 3ull * D.N || nt > 5ull * D.N || (nv && !vertices) || (nt && !triangles)) return HGS_EINVAL;
+  if (nv == 0 && nt == 0) return HGS_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const McPtrs p = mc_ptrs(carve_mc(D.N), const_cast<void*>(scratch));
+  hipLaunchKernelGGL(hgs_k_mc_emit, dim3((D.N + 255u) / 256u), dim3(256), 0, stream, D, field, threshold, p, nv, nt, vertices,
+                     triangles);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -969,6 +969,91 @@ std::tuple<Tensor, Tensor, c10::optional<Tensor>> mesh_query(const Tensor& point
   return {dist, face, uvw};
 }
 
+// ---- density field and marching cubes (include/hgs_rast.h: hgs_field_*, hgs_mc_*; the reference's extract_fields / mcubes) ----
+// (occ [R, R, R] fp32, block counts [nb, nb, nb] int32 or undefined, [center x, y, z, extent, scale], [num_kept, num_refs]).
+// One host wait (the plan's header sizes the lists).  Nothing kept: a zero field and no evaluation.
+std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64_t>> field_extract(
+    const Tensor& xyz, const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, const Tensor& axis,
+    int64_t num_blocks, double grow, bool want_counts) {
+  at::NoGradGuard ng;
+  const c10::Device dev = xyz.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  if (xyz.dim() != 2 || xyz.size(1) != 3) throw std::runtime_error("xyz must have dimensions (P, 3)");
+  const int64_t P = xyz.size(0), R = axis.numel();
+  if (P > 0x7fffffffll / 16) throw std::runtime_error("too many Gaussians");
+  if (opacity.numel() != P || scaling.numel() != 3 * P || rotation.numel() != 4 * P)
+    throw std::runtime_error("opacity (P[, 1]), scaling (P, 3) and rotation (P, 4) must match xyz (P, 3)");
+  if (axis.dim() != 1) throw std::runtime_error("axis must have dimensions (resolution,)");
+  if (num_blocks < 1 || num_blocks > 32 || R < num_blocks || R > 2048 || R % num_blocks != 0 || R / num_blocks > 256)
+    throw std::runtime_error("field: need 1 <= num_blocks <= 32, resolution <= 2048, resolution % num_blocks == 0 and "
+                             "resolution / num_blocks <= 256");
+  DeviceSwitch guard(dev.index());
+  const Tensor x = f32c(xyz, dev, "xyz"), o = f32c(opacity, dev, "opacity"), s = f32c(scaling, dev, "scaling"),
+               q = f32c(rotation, dev, "rotation"), ax = f32c(axis, dev, "axis");
+  const auto opts = at::TensorOptions().device(dev);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  const int32_t nb = (int32_t)num_blocks;
+  Tensor plan = at::empty({(int64_t)hgs_field_plan_bytes((int32_t)P, nb)}, opts.dtype(at::kByte));
+  Tensor info_dev = at::empty({(int64_t)sizeof(hgs_field_info)}, opts.dtype(at::kByte));
+  auto* info_ptr = reinterpret_cast<hgs_field_info*>(info_dev.data_ptr());
+  check_rc(hgs_field_plan((int32_t)P, fptr(x), fptr(o), fptr(s), fptr(q), (int32_t)R, nb, fptr(ax), (float)grow,
+                          plan.data_ptr(), info_ptr, stream), "hgs_field_plan");
+  hgs_field_info info;
+  if (hipMemcpyAsync(&info, info_ptr, sizeof(info), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    throw std::runtime_error("field_extract: reading the plan failed");
+  c10::optional<Tensor> counts;
+  const std::vector<double> geo = {info.center[0], info.center[1], info.center[2], info.extent, info.scale};
+  const std::vector<int64_t> sizes = {(int64_t)info.num_kept, (int64_t)info.num_refs};
+  if (info.num_refs == 0) {
+    if (want_counts) counts = at::zeros({num_blocks, num_blocks, num_blocks}, opts.dtype(at::kInt));
+    return {at::zeros({R, R, R}, opts.dtype(at::kFloat)), counts, geo, sizes};
+  }
+  const size_t bytes = hgs_field_list_bytes(&info);
+  if (bytes == 0)
+    throw std::runtime_error("field_extract: the plan is unusable (" + std::to_string(info.num_refs) +
+                             " list entries; at most 2^31 - 1)");
+  Tensor lists = at::empty({(int64_t)bytes}, opts.dtype(at::kByte));
+  Tensor occ = at::empty({R, R, R}, opts.dtype(at::kFloat));
+  if (want_counts) counts = at::empty({num_blocks, num_blocks, num_blocks}, opts.dtype(at::kInt));
+  check_rc(hgs_field_eval(&info, fptr(ax), plan.data_ptr(), lists.data_ptr(), occ.data_ptr<float>(),
+                          want_counts ? counts->data_ptr<int32_t>() : nullptr, stream), "hgs_field_eval");
+  return {occ, counts, geo, sizes};
+}
+
+// (vertices [V, 3] fp32 in index coordinates, triangles [T, 3] int32); one host wait for the two sizes
+std::tuple<Tensor, Tensor> marching_cubes(const Tensor& field, double threshold) {
+  at::NoGradGuard ng;
+  const c10::Device dev = field.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  if (field.dim() != 3) throw std::runtime_error("field must have dimensions (X, Y, Z)");
+  const auto opts = at::TensorOptions().device(dev);
+  const int64_t X = field.size(0), Y = field.size(1), Z = field.size(2);
+  if (X == 0 || Y == 0 || Z == 0)
+    return {at::empty({0, 3}, opts.dtype(at::kFloat)), at::empty({0, 3}, opts.dtype(at::kInt))};
+  if (X > (1 << 28) || Y > (1 << 28) || Z > (1 << 28)) throw std::runtime_error("marching_cubes: the field is too large");
+  const size_t bytes = hgs_mc_scratch_bytes((int32_t)X, (int32_t)Y, (int32_t)Z);
+  if (bytes == 0) throw std::runtime_error("marching_cubes: the field is too large (at most 2^28 samples)");
+  DeviceSwitch guard(dev.index());
+  const Tensor f = f32c(field, dev, "field");
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  Tensor scratch = at::empty({(int64_t)bytes}, opts.dtype(at::kByte));
+  Tensor info_dev = at::empty({(int64_t)sizeof(hgs_mc_info)}, opts.dtype(at::kByte));
+  auto* info_ptr = reinterpret_cast<hgs_mc_info*>(info_dev.data_ptr());
+  check_rc(hgs_mc_count(fptr(f), (int32_t)X, (int32_t)Y, (int32_t)Z, (float)threshold, scratch.data_ptr(), info_ptr, stream),
+           "hgs_mc_count");
+  hgs_mc_info info;
+  if (hipMemcpyAsync(&info, info_ptr, sizeof(info), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    throw std::runtime_error("marching_cubes: reading the sizes failed");
+  Tensor v = at::empty({(int64_t)info.num_vertices, 3}, opts.dtype(at::kFloat));
+  Tensor t = at::empty({(int64_t)info.num_triangles, 3}, opts.dtype(at::kInt));
+  check_rc(hgs_mc_emit(fptr(f), (int32_t)X, (int32_t)Y, (int32_t)Z, (float)threshold, scratch.data_ptr(), &info,
+                       info.num_vertices ? v.data_ptr<float>() : nullptr, info.num_triangles ? t.data_ptr<int32_t>() : nullptr,
+                       stream), "hgs_mc_emit");
+  return {v, t};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch binding of libhgs_rast.so (include/hgs_rast.h): autograd node, capacity logic, the one host wait";
   m.def("rasterize", &rasterize, py::call_guard<py::gil_scoped_release>());
@@ -990,6 +1075,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());
+  m.def("field_extract", &field_extract, py::arg("xyz"), py::arg("opacity"), py::arg("scaling"), py::arg("rotation"),
+        py::arg("axis"), py::arg("num_blocks"), py::arg("grow"), py::arg("want_counts") = false,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("marching_cubes", &marching_cubes, py::arg("field"), py::arg("threshold"), py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);
   m.def("abi_version", []() { return hgs_abi_version(); });

@@ -413,6 +413,80 @@ int hgs_mesh_grid_build(int32_t V, const float* vertices, int32_t F, const int32
 int hgs_mesh_query(int32_t P, const float* points, int32_t V, const float* vertices, int32_t F, const int32_t* faces,
                    const void* grid, int32_t mode, float* dist, int32_t* face, float* uvw, void* stream);
 
+/* ---- density field of the Gaussians and its iso-surface (the reference's mesh extraction) ----------------------------
+ * GaussianModel.extract_fields / extract_mesh of /root/reference/gs_renderer.py:240-361: a Python loop over 16^3 blocks
+ * there, followed by `mcubes.marching_cubes` on the CPU.  This definition is the contract:
+ *   - xyz [P][3], opacity [P] (ACTIVATED, in [0, 1]), scaling [P][3] (ACTIVATED standard deviations), rotation [P][4] (RAW
+ *     quaternion r, x, y, z; normalised here).  A Gaussian is KEPT iff opacity > 0.005 (and its centre is finite).
+ *   - center = (min + max) / 2 of the kept centres, extent = the box's largest side, scale = fp32(1.8 / extent) (the
+ *     division in fp64, as the reference's Python float); n = (xyz - center) * scale and s = scaling * scale in fp32.
+ *   - `axis` [resolution] fp32 holds the sample positions of every axis (the reference: torch.linspace(-1, 1, resolution)),
+ *     cut into num_blocks runs of resolution / num_blocks samples.  Block b of an axis spans lo_b = axis[first of run] -
+ *     grow .. hi_b = axis[last of run] + grow (fp32; the reference: grow = relax_ratio * 2 / num_blocks).  A kept Gaussian
+ *     is listed in block (bx, by, bz) iff lo < n < hi STRICTLY on all three axes; it then contributes to every sample of the
+ *     block and to no other sample.  resolution % num_blocks == 0, 1 <= num_blocks <= 32, resolution <= 2048,
+ *     resolution / num_blocks <= 256 (HGS_EINVAL otherwise).
+ *   - occ[x][y][z] = sum over the block's list, in ASCENDING Gaussian index, of opacity * exp(power), power = -1/2 d^T
+ *     Sigma^-1 d, d = sample - n; a term with power > 0 contributes 0.  fp32 throughout, one fixed instruction sequence:
+ *     the field is bit-reproducible from call to call (no floating-point atomics).
+ *   - Sigma^-1 is built as R diag(1 / s^2) R^T, NOT by the reference's adjugate of Sigma = R S^2 R^T with
+ *     1 / (det + 1e-24): the same matrix without the adjugate's cancellation (measured in fp32 against fp64 on an avatar
+ *     cloud: 4e-5 relative on the field instead of 4e-4).  The reference's + 1e-24 is not reproduced; it would change the
+ *     field by more than 1 % only where det Sigma = (s0 s1 s2)^2 < 1e-22, i.e. for Gaussians whose normalised scales have a
+ *     geometric mean below 2e-4 - a hundredth of the sample spacing at resolution 128.  exp(power) is evaluated as
+ *     exp2 of the form with log2(e) folded into the six coefficients.
+ * The lists' size depends on the data and the library does not allocate or synchronise, so a field takes two calls:
+ *   1. hgs_field_plan (scratch `plan`: hgs_field_plan_bytes) filters, reduces the box, writes one 10-float record and the
+ *      reached block range per Gaussian, counts every block's list and writes `info` (DEVICE);
+ *   2. the caller copies `info` to the host once, allocates hgs_field_list_bytes(&info_host) bytes (0: not a usable plan)
+ *      and calls hgs_field_eval with the same `axis` and `plan`.  num_kept == 0 (or a box of extent 0, which leaves no
+ *      finite normalised centre): every list is empty and the field is zero.
+ * block_counts (optional, [num_blocks]^3 int32, x-major like occ): the length of every block's list.
+ *
+ * hgs_mc_*: marching cubes of a field [X][Y][Z] fp32 (z fastest).  What it shares with `mcubes.marching_cubes` is the
+ * coordinates, the interpolation and the inside rule below - NOT the triangle list: the case table (csrc/mc_table.h) is
+ * this project's own, so in cells with an ambiguous face or a loop of five or more edges the triangles (and their number)
+ * may differ from mcubes', while the set of vertices is the same.  A field with a dimension of one sample has no cell and
+ * yields nothing (no vertices either).  Vertices
+ * in index coordinates ([0, X-1] x [0, Y-1] x [0, Z-1]), on the crossed grid edges at (threshold - f0) / (f1 - f0)
+ * between the edge's two samples.  A sample is INSIDE iff value >= threshold (NaN: outside).  ONE vertex per crossed
+ * grid edge, shared by the triangles around it; vertices in the memory order of the edges (by low grid point, then x, y, z
+ * direction), triangles in the memory order of the cells, inside a cell in the order of csrc/mc_table.h.  Triangles are
+ * wound so that their normals point from inside to outside (from high values to low): a closed surface around a
+ * maximum has positive signed volume.  Two calls again: hgs_mc_count classifies and scans (scratch: hgs_mc_scratch_bytes;
+ * X, Y, Z >= 1, X Y Z <= 2^28) and writes the sizes to `info` (DEVICE); the caller reads them, allocates vertices
+ * [num_vertices][3] fp32 and triangles [num_triangles][3] int32 and calls hgs_mc_emit with the same field and scratch.
+ * v17 gained these exports without a change of any earlier signature. */
+typedef struct hgs_field_info {
+  uint32_t bmin[3], bmax[3];  /* order-preserving integer images of the box of the kept centres (the plan's own use)   */
+  float center[3];
+  float extent;               /* largest side of the box                                                               */
+  float scale;                /* fp32(1.8 / extent)                                                                    */
+  uint32_t num_kept;
+  int32_t num_gaussians;      /* P of the plan                                                                         */
+  int32_t num_blocks;         /* per axis                                                                              */
+  int32_t resolution;
+  float grow;
+  uint64_t num_refs;          /* (Gaussian, block) references = the sum of all list lengths                            */
+} hgs_field_info;
+size_t hgs_field_plan_bytes(int32_t P, int32_t num_blocks);
+int hgs_field_plan(int32_t P, const float* xyz, const float* opacity, const float* scaling, const float* rotation,
+                   int32_t resolution, int32_t num_blocks, const float* axis, float grow, void* plan,
+                   hgs_field_info* info, void* stream);
+size_t hgs_field_list_bytes(const hgs_field_info* info_host);
+int hgs_field_eval(const hgs_field_info* info_host, const float* axis, const void* plan, void* lists, float* occ,
+                   int32_t* block_counts, void* stream);
+
+typedef struct hgs_mc_info {
+  uint32_t num_vertices;
+  uint32_t num_triangles;
+} hgs_mc_info;
+size_t hgs_mc_scratch_bytes(int32_t X, int32_t Y, int32_t Z);
+int hgs_mc_count(const float* field, int32_t X, int32_t Y, int32_t Z, float threshold, void* scratch, hgs_mc_info* info,
+                 void* stream);
+int hgs_mc_emit(const float* field, int32_t X, int32_t Y, int32_t Z, float threshold, const void* scratch,
+                const hgs_mc_info* info_host, float* vertices, int32_t* triangles, void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
