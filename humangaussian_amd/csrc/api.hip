@@ -1,6 +1,6 @@
 // api.hip - host side of the C ABI declared in include/hgs_rast.h: buffer carving and the
-// launch sequences.  No allocation, no host synchronisation; the only process-wide state is a per-device cache of
-// the CU count (read-only after its first use, filled under a mutex).
+// launch sequences.  No allocation, no host synchronisation; the only process-wide state is one DeviceState per device
+// (CU count, side stream, which kernels had their dynamic-LDS limit raised), each part filled at its first use.
 //
 // Forward launch chain (one stream, no host round trip), for all B views of a call at once:
 //   preprocess_fwd -> tiles -> fill (+ tile order) [status published] -> sort_{huge,large,lds} (+ cell lists,
@@ -42,28 +42,17 @@ inline int hgs_knob(const char* name, int dflt) { const char* e = getenv(name); 
 inline int hgs_knob(const char*, int dflt) { return dflt; }
 #endif
 
-// CUs of the device `stream` belongs to (persistent grids are sized by it).  Cached per device; the stream's device,
-// not the thread's current one.
-inline int cu_count(hipStream_t stream) {
-  static std::atomic<int> cache[64];
-  int dev = 0;
-  if (hipStreamGetDevice(stream, &dev) != hipSuccess) {
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-  }
-  if (dev < 0 || dev >= 64) return 256;
-  int c = cache[dev].load(std::memory_order_relaxed);
-  if (c > 0) return c;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  cache[dev].store(cus, std::memory_order_relaxed);
-  return cus;
-}
 #define HGS_CHUNK_ROWS_MIN_VIEWS 3     // calls with at least this many views keep the backward's pair rows chunk-cell-major (binning.hip::hgs_put_pair)
 #ifndef HGS_PRE_BWD_VPAR_MIN_VIEWS     // (a test build sets it above HGS_MAX_VIEWS: every multi-view call then takes the loop form)
 #define HGS_PRE_BWD_VPAR_MIN_VIEWS 2   // calls with at least this many views run the per-Gaussian backward with one thread per
                                        // (Gaussian, view); fewer: one thread per Gaussian
 #endif
 constexpr size_t ALIGN = 256;
+// carves one buffer into ALIGN-aligned pieces: take() -> the piece's offset; `off` ends as the buffer's size
+struct Carver {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; }
+};
 constexpr size_t HGS_LDS_BINS_MAX = 16384;   // T*4 bytes of LDS <= 64 KB
 #define HGS_BIN_WGS_PER_VIEW_MAX 512   // (256 until round 5: at 500k Gaussians a workgroup then walked 8 chunks one after the other -
                                        //  preprocess_fwd 70 -> 54 us with 512, +2 us in `tiles` (twice the histogram rows); 100k: +-0)
@@ -96,25 +85,24 @@ GeomCarve carve_geom(int B, int P, int H, int W) {
   bin_shape(B, P, nblk, cpw, nwg);
   const bool lds = T <= HGS_LDS_BINS_MAX;
   GeomCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
-  c.geom = take((size_t)B * P * sizeof(GeomRec));
-  c.tile_n = take(TT * 4);
-  c.tile_start = take(TT * 4);
-  c.tile_order = take(TT * 4);
-  c.tile_rec = take(TT * 16);
-  c.cell_info = take(TT * 16 * sizeof(CellInfo));
+  Carver cv;
+  c.geom = cv.take((size_t)B * P * sizeof(GeomRec));
+  c.tile_n = cv.take(TT * 4);
+  c.tile_start = cv.take(TT * 4);
+  c.tile_order = cv.take(TT * 4);
+  c.tile_rec = cv.take(TT * 16);
+  c.cell_info = cv.take(TT * 16 * sizeof(CellInfo));
   const size_t dcap = hgs_die_cells((int)TT);            // work tables are per die (Counters::sched)
-  c.items_part = take(HGS_NXCD * 2 * dcap * sizeof(uint4));   // last (partial) segment of every cell list, by length class
-  c.fwd_cells = take((size_t)HGS_NXCD * HGS_NFC * dcap * 4);    // non-empty cells by length class
-  c.hist = take(lds ? (size_t)B * nwg * T * 4 : 0);
-  c.tile_gbase = take(lds ? (size_t)HGS_ROW_GROUPS * TT * 4 : 0);
-  c.tile_count = take(lds ? 0 : TT * 4);
-  c.chunk_sums = take((size_t)B * nblk * 4);
-  c.chunk_base = take((size_t)B * nblk * 4);
-  c.ctr = take(sizeof(Counters));
-  c.status = take(sizeof(hgs_status));
-  c.total = off;
+  c.items_part = cv.take(HGS_NXCD * 2 * dcap * sizeof(uint4));   // last (partial) segment of every cell list, by length class
+  c.fwd_cells = cv.take((size_t)HGS_NXCD * HGS_NFC * dcap * 4);    // non-empty cells by length class
+  c.hist = cv.take(lds ? (size_t)B * nwg * T * 4 : 0);
+  c.tile_gbase = cv.take(lds ? (size_t)HGS_ROW_GROUPS * TT * 4 : 0);
+  c.tile_count = cv.take(lds ? 0 : TT * 4);
+  c.chunk_sums = cv.take((size_t)B * nblk * 4);
+  c.chunk_base = cv.take((size_t)B * nblk * 4);
+  c.ctr = cv.take(sizeof(Counters));
+  c.status = cv.take(sizeof(hgs_status));
+  c.total = cv.off;
   return c;
 }
 
@@ -124,18 +112,17 @@ struct BinCarve { size_t keys, recs, cell_list, entpair, cstate, items_full, tot
 // its tile (zoomed-in cameras), so no second capacity (and no second overflow path) exists.
 BinCarve carve_bin(int64_t cap) {
   BinCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  Carver cv;
   const size_t C = (size_t)(cap > 0 ? cap : 0);
   const size_t NP = C * HGS_PAIRS_PER_ENTRY;
-  c.keys = take(C * 8);
-  c.recs = take(C * sizeof(SortRec));
-  c.cell_list = take(NP * 8);
-  c.entpair = take(C * 8);
+  c.keys = cv.take(C * 8);
+  c.recs = cv.take(C * sizeof(SortRec));
+  c.cell_list = cv.take(NP * 8);
+  c.entpair = cv.take(C * 8);
   // a cell list of len entries has ceil(len / HGS_SEGLEN) - 1 stored states and ceil(len / HGS_SEGLEN) work items, len / HGS_SEGLEN of them full
-  c.cstate = take((NP / HGS_SEGLEN + 1) * HGS_CSTATE_FLOATS * sizeof(float));
-  c.items_full = take(HGS_NXCD * (NP / HGS_SEGLEN + 1) * sizeof(uint4));     // per die; one die's tiles may hold (nearly) all full segments
-  c.total = off;
+  c.cstate = cv.take((NP / HGS_SEGLEN + 1) * HGS_CSTATE_FLOATS * sizeof(float));
+  c.items_full = cv.take(HGS_NXCD * (NP / HGS_SEGLEN + 1) * sizeof(uint4));     // per die; one die's tiles may hold (nearly) all full segments
+  c.total = cv.off;
   return c;
 }
 
@@ -233,24 +220,81 @@ struct SideStream {
   hipEvent_t fork = nullptr, join = nullptr;
   bool tried = false, ok = false;
 };
-SideStream* side_stream_for(hipStream_t stream) {
-  static SideStream tab[64];
+
+// Everything the host remembers per device, looked up once per call by the STREAM's device (not the thread's current
+// one).  One failure rule: a stream whose device cannot be determined has no state (device_state() == nullptr), and every
+// reader below then gives its most conservative answer - 256 CUs, no side stream, no LDS raise (=> the loop form of the
+// per-Gaussian backward); no other device's entry is read or written.
+struct DeviceState {
+  std::atomic<int> cus;                             // 0: not asked yet
+  SideStream side;
+  std::atomic<int> lds_raised[HGS_PRE_BWD_ROWS];    // per row of hgs_pre_bwd_forms: 0 not tried, 1 raised to 160 KB, -1 refused
+};
+DeviceState g_devices[64];
+DeviceState* device_state(hipStream_t stream) {
   int dev = 0;
   if (hipStreamGetDevice(stream, &dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return nullptr; }
-  SideStream& t = tab[dev];
+  return &g_devices[dev];
+}
+// the state's device made current (stream / event creation and function attributes act on the current device); the
+// caller's comes back at the end of the scope.  !ok (the current device cannot be read or switched): the same failure
+// rule - the caller creates / raises nothing rather than act on a device it does not know
+struct DeviceCurrent {
+  int dev, cur = 0;
+  bool ok, switched;
+  explicit DeviceCurrent(const DeviceState* ds)
+      : dev((int)(ds - g_devices)), ok(hipGetDevice(&cur) == hipSuccess), switched(ok && cur != dev) {
+    if (switched) ok = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceCurrent() { if (switched) (void)hipSetDevice(cur); }
+};
+
+// CUs of the stream's device (persistent grids are sized by it)
+int cu_count(DeviceState* ds) {
+  if (!ds) return 256;
+  int cus = ds->cus.load(std::memory_order_relaxed);
+  if (cus > 0) return cus;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, (int)(ds - g_devices)) != hipSuccess || cus < 1) cus = 256;
+  ds->cus.store(cus, std::memory_order_relaxed);
+  return cus;
+}
+
+// the device's side stream and its two events, created at the first call that wants them; nullptr: stay on the caller's stream
+SideStream* side_stream(DeviceState* ds) {
+  if (!ds) return nullptr;
+  SideStream& t = ds->side;
   std::lock_guard<std::mutex> lk(t.mu);
   if (!t.tried) {
     t.tried = true;
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    if (have_cur && cur != dev) (void)hipSetDevice(dev);
-    t.ok = hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) == hipSuccess &&
+    DeviceCurrent on(ds);
+    t.ok = on.ok && hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) == hipSuccess &&
            hipEventCreateWithFlags(&t.fork, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&t.join, hipEventDisableTiming) == hipSuccess;
-    if (have_cur && cur != dev) (void)hipSetDevice(cur);
     if (!t.ok) (void)hipGetLastError();
   }
   return t.ok ? &t : nullptr;
+}
+
+// May row `row` of hgs_pre_bwd_forms be launched with more than 64 KB of dynamic LDS on this device?  The attribute
+// is raised ONCE per (device, row) to the CU's whole LDS and remembered: a driver call per backward was host time on the
+// hot path; a refusal is remembered too (and said once on stderr): the loop form then serves.
+bool pre_bwd_lds_raised(DeviceState* ds, int row) {
+  if (!ds) return false;
+  int st = ds->lds_raised[row].load(std::memory_order_relaxed);
+  if (st == 0) {
+    const PreBwdForm& form = hgs_pre_bwd_forms.row[row];
+    DeviceCurrent on(ds);
+    if (on.ok && hipFuncSetAttribute(reinterpret_cast<const void*>(form.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) {
+      st = 1;
+    } else {
+      (void)hipGetLastError();
+      st = -1;
+      fprintf(stderr, "libhgs_rast: cannot raise the dynamic LDS limit of %s on device %d: "
+                      "batches that need more than 64 KB take the (slower) loop form\n", form.name, on.dev);
+    }
+    ds->lds_raised[row].store(st, std::memory_order_relaxed);
+  }
+  return st > 0;
 }
 
 bool settings_ok(const hgs_settings* s) {
@@ -306,15 +350,14 @@ KnnCarve carve_knn(int32_t P) {
   const size_t n = (size_t)(P > 0 ? P : 0);
   const size_t want = std::max<size_t>(64, 2 * n);
   c.nc_max = (uint32_t)std::min<size_t>(want, HGS_KNN_MAX_CELLS);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
-  c.grid = take(sizeof(KnnGrid));
-  c.cell_of = take(n * 4);
-  c.count = take(((size_t)c.nc_max + 1) * 4);
-  c.cursor = take((size_t)c.nc_max * 4);
-  c.bsum = take(((size_t)c.nc_max / 1024 + 2) * 4);
-  c.sorted = take(n * 16);
-  c.total = off;
+  Carver cv;
+  c.grid = cv.take(sizeof(KnnGrid));
+  c.cell_of = cv.take(n * 4);
+  c.count = cv.take(((size_t)c.nc_max + 1) * 4);
+  c.cursor = cv.take((size_t)c.nc_max * 4);
+  c.bsum = cv.take(((size_t)c.nc_max / 1024 + 2) * 4);
+  c.sorted = cv.take(n * 16);
+  c.total = cv.off;
   return c;
 }
 }  // namespace
@@ -465,7 +508,8 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
   // entry ids travel in 27 bits (entpair.x = entry | pairs << 27): a larger list cannot be addressed
   if (entry_capacity > HGS_MAX_ENTRY_CAPACITY) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int ncu = cu_count(stream);
+  DeviceState* const ds = device_state(stream);
+  const int ncu = cu_count(ds);
   // (the gradient bit belongs to the backward: masked out, so that no forward kernel can ever branch on it; the
   // antialiasing bit selects the forward kernel, not a branch in it)
   const bool aa = (activation_flags & HGS_ANTIALIAS) != 0;
@@ -539,7 +583,7 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
     // (the side stream costs a cross-stream edge, ~11 us at the join: it is taken when a long list is EXPECTED - a hint
     // beyond 1.5 x the class boundary, i.e. a list the caller has seen, not the margin on a shorter one - or unknown)
     const bool expect_long = hint <= 0 || hint > HGS_SORT_LDS_MAX + HGS_SORT_LDS_MAX / 2 + 64;
-    SideStream* side = ((need_huge || need_large) && expect_long) ? side_stream_for(stream) : nullptr;
+    SideStream* side = ((need_huge || need_large) && expect_long) ? side_stream(ds) : nullptr;
     {
       std::unique_lock<std::mutex> side_lk;
       hipStream_t s2 = stream;
@@ -564,10 +608,8 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
       }
       // persistent workgroups (53 KB of LDS: three per CU), tiles heavy first round-robin
       const unsigned sort_wgs = std::min<unsigned>(class_grid(1), (unsigned)(hgs_knob("HGS_SORT_WGS_PER_CU", 3) * ncu));
-      if (v.pairchunks)
-        hipLaunchKernelGGL(hgs_k_sort_lds_ch, dim3(sort_wgs), dim3(HGS_SORT_NT), 0, stream, v, L, status_dev);
-      else
-        hipLaunchKernelGGL(hgs_k_sort_lds, dim3(sort_wgs), dim3(HGS_SORT_NT), 0, stream, v, L, status_dev);
+      hipLaunchKernelGGL(v.pairchunks ? hgs_k_sort_lds_ch : hgs_k_sort_lds, dim3(sort_wgs), dim3(HGS_SORT_NT), 0, stream, v, L,
+                         status_dev);
       HGS_LAUNCH_CHECK();
       if (side) {                                        // join: the blend needs every class
         e = hipStreamWaitEvent(stream, side->join, 0);
@@ -587,12 +629,9 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
     const int64_t fwd_blocks = (int64_t)hgs_knob("HGS_FWD_BLOCKS_PER_CU", 4) * ncu;
     const unsigned cell_blocks = (unsigned)std::max<int64_t>(4, std::min<int64_t>(fwd_blocks, (cells + 3) / 4) & ~int64_t(3));
     const unsigned bg_blocks = (unsigned)v.TT;
-    if (store_bwd_state)
-      hipLaunchKernelGGL(hgs_k_render_fwd_store, dim3(cell_blocks + bg_blocks), dim3(HGS_FWD_THREADS), 0, stream, v, L, cell_blocks,
-                         status_dev, status_mapped, L.recs, L.cstate, out_color, out_depth, out_alpha);
-    else
-      hipLaunchKernelGGL(hgs_k_render_fwd_nostore, dim3(cell_blocks + bg_blocks), dim3(HGS_FWD_THREADS), 0, stream, v, L, cell_blocks,
-                         status_dev, status_mapped, L.recs, L.cstate, out_color, out_depth, out_alpha);
+    hipLaunchKernelGGL(store_bwd_state ? hgs_k_render_fwd_store : hgs_k_render_fwd_nostore, dim3(cell_blocks + bg_blocks),
+                       dim3(HGS_FWD_THREADS), 0, stream, v, L, cell_blocks, status_dev, status_mapped, L.recs, L.cstate,
+                       out_color, out_depth, out_alpha);
   }
   HGS_LAUNCH_CHECK();
   HGS_STAGE(5);
@@ -658,6 +697,7 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
   const bool maybe_entries = status ? status->num_rendered > 0 : entry_capacity > 0;
   if (maybe_entries && (!bin || !bwd_scratch)) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  DeviceState* const ds = device_state(stream);
   const int64_t cap = entry_capacity;
   const View v = make_view(s, B, P, M, cap, 0, activation_flags);
   const Layout L = make_layout(const_cast<void*>(geom), const_cast<void*>(bin),
@@ -678,7 +718,7 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
   if (maybe_entries) {
     // persistent workgroups of HGS_BWD_BLOCK_WAVES waves: as many waves as the chip holds (LDS: 11.8 KB per wave =>
     // 12 per CU, 3 per SIMD); the waves of a workgroup draw its groups of four work items through an LDS ticket
-    const int resident = hgs_knob("HGS_BWD_WAVES_PER_CU", 12) * cu_count(stream);
+    const int resident = hgs_knob("HGS_BWD_WAVES_PER_CU", 12) * cu_count(ds);
     hipLaunchKernelGGL(hgs_k_render_bwd, dim3((unsigned)std::max(HGS_NXCD, resident / HGS_BWD_BLOCK_WAVES / HGS_NXCD * HGS_NXCD)), dim3(64 * HGS_BWD_BLOCK_WAVES), 0, stream, v, L, status_dev, L.recs, L.cstate,
                        out_color, out_depth, out_alpha, dL_dout_color, dL_dout_depth, dL_dout_alpha, pair_rows, pair_cap);
     HGS_LAUNCH_CHECK();
@@ -686,93 +726,37 @@ int backward_impl(const hgs_settings* s, int32_t B, int32_t P, int32_t M, const 
     if (X > 0) {
       // a caller that holds the status hands the reduction its entry count (no status round trip in front of its chain)
       const uint32_t R_host = status ? status->num_rendered : 0xffffffffu;
-      if (v.pairchunks)
-        hipLaunchKernelGGL(hgs_k_pair_reduce_ch, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, stream, v, L, status_dev, L.recs,
-                           pair_rows, rows, pair_cap, R_host);
-      else
-        hipLaunchKernelGGL(hgs_k_pair_reduce_em, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, stream, v, L, status_dev, L.recs,
-                           pair_rows, rows, pair_cap, R_host);
+      hipLaunchKernelGGL(v.pairchunks ? hgs_k_pair_reduce_ch : hgs_k_pair_reduce_em, dim3((unsigned)((X + 255) / 256)), dim3(256), 0,
+                         stream, v, L, status_dev, L.recs, pair_rows, rows, pair_cap, R_host);
       HGS_LAUNCH_CHECK();
     }
   }
   if (!maybe_entries) HGS_STAGE(1);
   HGS_STAGE(2);
-#define HGS_LAUNCH_PRE_BWD(K, GRID, THREADS, LDS)                                                     \
-  hipLaunchKernelGGL(K, dim3(GRID), dim3(THREADS), LDS, stream, v, L, status_dev, rows, means3D, shs, \
-                     colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dmeans2D, \
-                     dL_dshs, dL_dcolors_precomp, dL_dopacities, dL_dscales, dL_drotations,            \
-                     dL_dcov3D_precomp, pack, (int)pack_F)
   // One view: the instantiation without the loop over views (94 instead of 176 VGPRs at SH degree 0).  Several
   // views: one thread per (Gaussian, view) - a workgroup of B waves per 64 Gaussians, summed in view order
   // through LDS (preprocess.hip, mode 2); combinations whose exchange buffer would not fit: the loop.
   const int deg = shs ? v.D : 0;
   const int nc = (deg + 1) * (deg + 1);
   const int aa = (activation_flags & HGS_ANTIALIAS) ? 1 : 0;   // (the filter's copies of the kernels; d3 switches at run time)
-  const unsigned thr_p = 64u * (unsigned)v.B, grid_p = (unsigned)((v.P + 63) / 64);
+  const unsigned thr_p = 64u * (unsigned)v.B;
   const size_t lds_p = (size_t)(23 + 3 * nc) * thr_p * sizeof(float);
   // The exchange buffer may take the CU's whole LDS (160 KB on gfx950; beyond 64 KB the kernel's dynamic-LDS limit is raised
-  // first): 16 views at SH degrees 0 / 1, 8 at degrees 2 / 3 (139 KB at degree 3) - the thread-per-(Gaussian, view) form
-  // then covers every batch a training step makes; the loop form (d*: 256 VGPRs at degree 3, one wave per SIMD) remains
-  // for what does not fit or when the limit cannot be raised.
-  bool vpar_ok = v.B >= HGS_PRE_BWD_VPAR_MIN_VIEWS && v.B <= (deg >= 2 ? 8 : 16) && lds_p <= 160 * 1024;
-  if (vpar_ok && lds_p > 65536) {
-    // the attribute is raised ONCE per (device, kernel) to the CU's whole LDS and remembered: a driver call per backward
-    // was host time on the hot path; a refusal is remembered too (and said once on stderr): the loop form then serves
-    static std::atomic<int> lds_raised[64][8];          // [device][deg + 4 aa] 0: not tried, 1: raised to 160 KB, -1: refused
-    int dev = 0;
-    if (hipStreamGetDevice(stream, &dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int st = lds_raised[dev][deg + 4 * aa].load(std::memory_order_relaxed);
-    if (st == 0) {
-      const void* const kfns[8] = {reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p0),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p1),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p2),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p3),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p0_aa),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p1_aa),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p2_aa),
-                                   reinterpret_cast<const void*>(hgs_k_preprocess_bwd_p3_aa)};
-      const void* kfn = kfns[deg + 4 * aa];
-      if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) {
-        st = 1;
-      } else {
-        (void)hipGetLastError();
-        st = -1;
-        fprintf(stderr, "libhgs_rast: cannot raise the dynamic LDS limit of hgs_k_preprocess_bwd_p%d%s on device %d: "
-                        "batches that need more than 64 KB take the (slower) loop form\n", deg, aa ? "_aa" : "", dev);
-      }
-      lds_raised[dev][deg + 4 * aa].store(st, std::memory_order_relaxed);
-    }
-    if (st < 0) vpar_ok = false;
-  }
+  // first): with the launch bounds of hgs_pre_bwd_forms 16 views at SH degrees 0 / 1, 8 at degrees 2 / 3 (139 KB at degree 3)
+  // - the thread-per-(Gaussian, view) form then covers every batch a training step makes; the loop form (d*: 256 VGPRs at
+  // degree 3, one wave per SIMD) remains for what does not fit or when the limit cannot be raised.
+  const int row_p = hgs_pre_bwd_row(aa, 2, deg);
+  const bool vpar_ok = v.B >= HGS_PRE_BWD_VPAR_MIN_VIEWS && thr_p <= (unsigned)hgs_pre_bwd_forms.row[row_p].threads &&
+                       (lds_p <= 65536 || pre_bwd_lds_raised(ds, row_p));
   const int mode = v.B == 1 ? 1 : (vpar_ok ? 2 : 0);
-  const size_t lds_s = hgs_pre_bwd_stage_bytes(M, deg, shs != nullptr && dL_dshs != nullptr);      // (<= 53 KB)
-  switch (deg + 4 * mode + 12 * aa) {
-    case 0: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d0, v.nblk, HGS_BLOCK, 0); break;
-    case 1: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d1, v.nblk, HGS_BLOCK, 0); break;
-    case 2: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d2, v.nblk, HGS_BLOCK, 0); break;
-    case 3: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d3, v.nblk, HGS_BLOCK, 0); break;
-    case 4: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s0, v.nblk, HGS_BLOCK, 0); break;
-    case 5: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s1, v.nblk, HGS_BLOCK, lds_s); break;      // (SH blocks through LDS)
-    case 6: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s2, v.nblk, HGS_BLOCK, lds_s); break;
-    case 7: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s3, v.nblk, HGS_BLOCK, lds_s); break;
-    case 8: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p0, grid_p, thr_p, lds_p); break;
-    case 9: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p1, grid_p, thr_p, lds_p); break;
-    case 10: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p2, grid_p, thr_p, lds_p); break;
-    case 11: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p3, grid_p, thr_p, lds_p); break;
-    case 12: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d0_aa, v.nblk, HGS_BLOCK, 0); break;
-    case 13: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d1_aa, v.nblk, HGS_BLOCK, 0); break;
-    case 14: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d2_aa, v.nblk, HGS_BLOCK, 0); break;
-    case 15: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_d3, v.nblk, HGS_BLOCK, 0); break;       // (v.act carries the bit)
-    case 16: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s0_aa, v.nblk, HGS_BLOCK, 0); break;
-    case 17: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s1_aa, v.nblk, HGS_BLOCK, lds_s); break;
-    case 18: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s2_aa, v.nblk, HGS_BLOCK, lds_s); break;
-    case 19: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_s3_aa, v.nblk, HGS_BLOCK, lds_s); break;
-    case 20: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p0_aa, grid_p, thr_p, lds_p); break;
-    case 21: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p1_aa, grid_p, thr_p, lds_p); break;
-    case 22: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p2_aa, grid_p, thr_p, lds_p); break;
-    default: HGS_LAUNCH_PRE_BWD(hgs_k_preprocess_bwd_p3_aa, grid_p, thr_p, lds_p); break;
-  }
-#undef HGS_LAUNCH_PRE_BWD
+  const PreBwdForm& form = hgs_pre_bwd_forms.row[hgs_pre_bwd_row(aa, mode, deg)];
+  // s, d: a thread per Gaussian (s at degree >= 1: SH blocks through LDS, <= 53 KB); p: a wave per view of 64 Gaussians
+  const unsigned grid = mode == 2 ? (unsigned)((v.P + 63) / 64) : (unsigned)v.nblk, threads = mode == 2 ? thr_p : HGS_BLOCK;
+  const size_t lds = mode == 2 ? lds_p : (mode == 1 ? hgs_pre_bwd_stage_bytes(M, deg, shs != nullptr && dL_dshs != nullptr) : 0);
+  hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(threads), lds, stream, v, L, status_dev, rows, means3D, shs,
+                     colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dmeans2D,
+                     dL_dshs, dL_dcolors_precomp, dL_dopacities, dL_dscales, dL_drotations,
+                     dL_dcov3D_precomp, pack, (int)pack_F);
   HGS_LAUNCH_CHECK();
   HGS_STAGE(3);
   return HGS_OK;
@@ -934,15 +918,14 @@ namespace {
 struct MeshCarve { size_t tris, start, cursor, bsum, refs, total; };
 MeshCarve carve_mesh(int32_t F, uint32_t ncells, uint64_t nrefs) {
   MeshCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
-  take(sizeof(MeshGridHdr));
-  c.tris = take((size_t)F * 48);
-  c.start = take(((size_t)ncells + 1) * 4);
-  c.cursor = take((size_t)ncells * 4);
-  c.bsum = take(((size_t)ncells / 1024 + 2) * 4);
-  c.refs = take((size_t)nrefs * 4);
-  c.total = off;
+  Carver cv;
+  cv.take(sizeof(MeshGridHdr));
+  c.tris = cv.take((size_t)F * 48);
+  c.start = cv.take(((size_t)ncells + 1) * 4);
+  c.cursor = cv.take((size_t)ncells * 4);
+  c.bsum = cv.take(((size_t)ncells / 1024 + 2) * 4);
+  c.refs = cv.take((size_t)nrefs * 4);
+  c.total = cv.off;
   return c;
 }
 bool mesh_info_ok(const hgs_mesh_grid_info* in) {
@@ -1029,25 +1012,23 @@ namespace {
 struct FieldPlanCarve { size_t rec, reach, bounds, counts, total; };
 FieldPlanCarve carve_field_plan(int32_t P, int32_t nb) {
   FieldPlanCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
-  c.rec = take((size_t)P * HGS_FIELD_REC_FLOATS * 4);
-  c.reach = take((size_t)P * 4);
-  c.bounds = take(2 * HGS_FIELD_MAX_BLOCKS * 4);
-  c.counts = take((size_t)nb * nb * nb * 4);
-  c.total = off;
+  Carver cv;
+  c.rec = cv.take((size_t)P * HGS_FIELD_REC_FLOATS * 4);
+  c.reach = cv.take((size_t)P * 4);
+  c.bounds = cv.take(2 * HGS_FIELD_MAX_BLOCKS * 4);
+  c.counts = cv.take((size_t)nb * nb * nb * 4);
+  c.total = cv.off;
   return c;
 }
 struct FieldListCarve { size_t start, order, refs, total; };
 FieldListCarve carve_field_lists(int32_t nb, uint64_t nrefs) {
   FieldListCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
+  Carver cv;
   const size_t nblocks = (size_t)nb * nb * nb;
-  c.start = take((nblocks + 1) * 4);
-  c.order = take(nblocks * 4);
-  c.refs = take((size_t)nrefs * 4);
-  c.total = off;
+  c.start = cv.take((nblocks + 1) * 4);
+  c.order = cv.take(nblocks * 4);
+  c.refs = cv.take((size_t)nrefs * 4);
+  c.total = cv.off;
   return c;
 }
 bool field_dims_ok(int32_t P, int32_t R, int32_t nb) {
@@ -1075,12 +1056,11 @@ bool mc_dims_ok(int32_t X, int32_t Y, int32_t Z) {
 }
 McCarve carve_mc(size_t N) {
   McCarve c;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; };
-  c.offs = take((N + 1) * 8);
-  c.bsum = take(((N + 1023) / 1024 + 1) * 8);
-  c.mask = take(N);
-  c.total = off;
+  Carver cv;
+  c.offs = cv.take((N + 1) * 8);
+  c.bsum = cv.take(((N + 1023) / 1024 + 1) * 8);
+  c.mask = cv.take(N);
+  c.total = cv.off;
   return c;
 }
 McPtrs mc_ptrs(const McCarve& c, void* scratch) {

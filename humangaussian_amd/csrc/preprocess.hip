@@ -495,22 +495,17 @@ namespace {
 // AA: the antialiasing filter's chain rule (HGS_ANTIALIAS); 0: off, 1: on, 2: decided at run time from v.act (the one
 // form whose compile-time copy would not fit its registers: the loop over the views at SH degree 3).
 //
-// Which kernel serves which call (api.hip, the switch behind HGS_LAUNCH_PRE_BWD; D = the active SH degree, 0 with
-// colors_precomp whatever the settings say; `_aa` = the filter's copy):
-//
-//   views B   D = 0         D = 1         D = 2         D = 3
-//   1         s0 / s0_aa    s1 / s1_aa    s2 / s2_aa    s3 / s3_aa     (D >= 1, 4 <= M <= 16, six tensors: SH blocks of full
-//                                                                       256-chunks through LDS; else 16 B vectors when
-//                                                                       3 M % 4 == 0 and M <= 16; else scalars)
-//   2 .. 8    p0 / p0_aa    p1 / p1_aa    p2 / p2_aa    p3 / p3_aa     (exchange buffer (23 + 3 (D+1)^2) * 64 B floats of LDS;
-//   9 .. 16   p0 / p0_aa    p1 / p1_aa    d2 / d2_aa    d3 / d3 + bit    above 64 KB - from 10 views at D = 0, 8 at D = 1,
-//                                                                        6 at D = 2, 4 at D = 3 - the dynamic-LDS limit is
-//                                                                        raised first)
-//
-// d0, d1, d0_aa, d1_aa serve only where that raise is refused (then also d2 / d3 for the calls above 64 KB) or
-// in a build with HGS_PRE_BWD_VPAR_MIN_VIEWS above HGS_MAX_VIEWS (api.hip), which sends every multi-view call through
-// the loop: tests/test_gpu_pre_bwd_matrix.py builds that twin to run them and to compare the two forms bit for bit.
-// 24 targets, 23 kernels: d3 serves the filter through v.act.
+// Which kernels exist, with which launch bound: HGS_PRE_BWD_FORMS below the body, one row per kernel.  The host's table
+// is generated from it; api.hip's backward_impl looks a call's row up by (filter, mode, active SH degree D - 0 with
+// colors_precomp whatever the settings say).  What the rows do not say:
+//  - mode: one view takes `s`; several take `p` while a wave per view fits the row's launch bound and the exchange
+//    buffer of (23 + 3 (D+1)^2) * 64 B floats is granted (above 64 KB the kernel's dynamic-LDS limit is raised first);
+//    the rest loops (`d`).  So d0, d1, d0_aa, d1_aa serve only where that raise is refused, or in a build with
+//    HGS_PRE_BWD_VPAR_MIN_VIEWS above HGS_MAX_VIEWS (api.hip), which sends every multi-view call through the loop:
+//    tests/test_gpu_pre_bwd_matrix.py builds that twin to run them and to compare the two forms bit for bit.
+//  - 24 (filter, mode, degree) combinations, 23 kernels: `d3` alone decides the filter at run time (AA 2 above).
+//  - the SH paths: only `s` (full 256-chunks, D >= 1, 4 <= M <= 16, six tensors) moves its SH blocks through LDS - its
+//    workgroup owns a contiguous range of them; elsewhere 16 B vectors when 3 M % 4 == 0 and M <= 16, else scalars.
 template <int DEG, int MODE, int AA>
 __device__ __forceinline__ void preprocess_bwd_body(
     const View& v, const Layout& L, const hgs_status* __restrict__ status,
@@ -1001,7 +996,36 @@ __device__ __forceinline__ void preprocess_bwd_body(
 
 }  // namespace
 
-#define HGS_PRE_BWD_KERNEL(DEG, NAME, MODE, THREADS, AA)                                                 \
+// THE table of the family: one row per kernel, (DEG, MODE, AA, NAME, THREADS) - the body's template arguments, the
+// exported name (d: MODE 0, s: 1, p: 2) and the launch bound.  The kernels below and the host's table behind them
+// (hgs_pre_bwd_forms: what api.hip launches, and how many views a `p` form takes) are both generated from it.
+#define HGS_PRE_BWD_FORMS(X)                                                                                              \
+  X(0, 0, 0, hgs_k_preprocess_bwd_d0, HGS_BLOCK)      /* thread per Gaussian, loop over the views */                       \
+  X(1, 0, 0, hgs_k_preprocess_bwd_d1, HGS_BLOCK)                                                                          \
+  X(2, 0, 0, hgs_k_preprocess_bwd_d2, HGS_BLOCK)                                                                          \
+  X(3, 0, 2, hgs_k_preprocess_bwd_d3, HGS_BLOCK)      /* AA 2: ONE kernel for filter off and on (v.act), see above */      \
+  X(0, 1, 0, hgs_k_preprocess_bwd_s0, HGS_BLOCK)      /* one view */                                                       \
+  X(1, 1, 0, hgs_k_preprocess_bwd_s1, HGS_BLOCK)                                                                          \
+  X(2, 1, 0, hgs_k_preprocess_bwd_s2, HGS_BLOCK)                                                                          \
+  X(3, 1, 0, hgs_k_preprocess_bwd_s3, HGS_BLOCK)                                                                          \
+  X(0, 2, 0, hgs_k_preprocess_bwd_p0, 1024)           /* thread per (Gaussian, view), a wave per view: serves up to */     \
+  X(1, 2, 0, hgs_k_preprocess_bwd_p1, 1024)           /* THREADS / 64 views (SH degree >= 2: 512, registers / LDS) */      \
+  X(2, 2, 0, hgs_k_preprocess_bwd_p2, 512)                                                                                \
+  X(3, 2, 0, hgs_k_preprocess_bwd_p3, 512)                                                                                \
+  /* with the antialiasing filter (HGS_ANTIALIAS): compile-time copies of every form but the SH-3 loop (d3 above) */     \
+  X(0, 0, 1, hgs_k_preprocess_bwd_d0_aa, HGS_BLOCK)                                                                       \
+  X(1, 0, 1, hgs_k_preprocess_bwd_d1_aa, HGS_BLOCK)                                                                       \
+  X(2, 0, 1, hgs_k_preprocess_bwd_d2_aa, HGS_BLOCK)                                                                       \
+  X(0, 1, 1, hgs_k_preprocess_bwd_s0_aa, HGS_BLOCK)                                                                       \
+  X(1, 1, 1, hgs_k_preprocess_bwd_s1_aa, HGS_BLOCK)                                                                       \
+  X(2, 1, 1, hgs_k_preprocess_bwd_s2_aa, HGS_BLOCK)                                                                       \
+  X(3, 1, 1, hgs_k_preprocess_bwd_s3_aa, HGS_BLOCK)                                                                       \
+  X(0, 2, 1, hgs_k_preprocess_bwd_p0_aa, 1024)                                                                            \
+  X(1, 2, 1, hgs_k_preprocess_bwd_p1_aa, 1024)                                                                            \
+  X(2, 2, 1, hgs_k_preprocess_bwd_p2_aa, 512)                                                                             \
+  X(3, 2, 1, hgs_k_preprocess_bwd_p3_aa, 512)
+
+#define HGS_PRE_BWD_KERNEL(DEG, MODE, AA, NAME, THREADS)                                                 \
   extern "C" __global__ void __launch_bounds__(THREADS) NAME(                                       \
       View v, Layout L, const hgs_status* __restrict__ status, const float* __restrict__ grad_rows, \
       const float* __restrict__ means3D, const float* __restrict__ shs,                             \
@@ -1015,30 +1039,43 @@ __device__ __forceinline__ void preprocess_bwd_body(
                              rotations, cov3D_precomp, dL_dmeans3D, dL_dmeans2D, dL_dshs,           \
                              dL_dcolors, dL_dopac, dL_dscales, dL_drots, dL_dcov3D, pack, pack_F);  \
   }
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_d0, 0, HGS_BLOCK, 0)         // thread per Gaussian, loop over the views
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_d1, 0, HGS_BLOCK, 0)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_d2, 0, HGS_BLOCK, 0)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_d3, 0, HGS_BLOCK, 2)         // (antialiasing: a run-time switch, see above)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_s0, 1, HGS_BLOCK, 0)         // single-view instantiations
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_s1, 1, HGS_BLOCK, 0)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_s2, 1, HGS_BLOCK, 0)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_s3, 1, HGS_BLOCK, 0)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_p0, 2, 1024, 0)   // thread per (Gaussian, view): up to 16 views (SH degree >= 2: 8, registers / LDS)
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_p1, 2, 1024, 0)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_p2, 2, 512, 0)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_p3, 2, 512, 0)
-// with the antialiasing filter (HGS_ANTIALIAS): compile-time copies of every form but the SH-3 loop (d3 above)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_d0_aa, 0, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_d1_aa, 0, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_d2_aa, 0, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_s0_aa, 1, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_s1_aa, 1, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_s2_aa, 1, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_s3_aa, 1, HGS_BLOCK, 1)
-HGS_PRE_BWD_KERNEL(0, hgs_k_preprocess_bwd_p0_aa, 2, 1024, 1)
-HGS_PRE_BWD_KERNEL(1, hgs_k_preprocess_bwd_p1_aa, 2, 1024, 1)
-HGS_PRE_BWD_KERNEL(2, hgs_k_preprocess_bwd_p2_aa, 2, 512, 1)
-HGS_PRE_BWD_KERNEL(3, hgs_k_preprocess_bwd_p3_aa, 2, 512, 1)
+HGS_PRE_BWD_FORMS(HGS_PRE_BWD_KERNEL)
+#undef HGS_PRE_BWD_KERNEL
+
+namespace {
+// The host's view of the table: row (aa, mode, deg) -> the kernel that serves it (all of one signature), its name and its
+// launch bound.  An AA-2 row fills both of its filter slots.
+using PreBwdKernel = void (*)(View, Layout, const hgs_status*, const float*, const float*, const float*, const float*,
+                              const float*, const float*, const float*, const float*, float*, float*, float*, float*,
+                              float*, float*, float*, float*, float*, int);
+struct PreBwdForm { PreBwdKernel kernel; const char* name; int threads; };
+constexpr int HGS_PRE_BWD_ROWS = 24;
+constexpr int hgs_pre_bwd_row(int aa, int mode, int deg) { return deg + 4 * mode + 12 * aa; }
+struct PreBwdForms { PreBwdForm row[HGS_PRE_BWD_ROWS]; };
+__host__ constexpr PreBwdForms hgs_make_pre_bwd_forms() {
+  PreBwdForms t{};
+#define HGS_PRE_BWD_ROW(DEG, MODE, AA, NAME, THREADS)                                      \
+  if (AA != 1) t.row[hgs_pre_bwd_row(0, MODE, DEG)] = PreBwdForm{NAME, #NAME, THREADS};    \
+  if (AA != 0) t.row[hgs_pre_bwd_row(1, MODE, DEG)] = PreBwdForm{NAME, #NAME, THREADS};
+  HGS_PRE_BWD_FORMS(HGS_PRE_BWD_ROW)
+#undef HGS_PRE_BWD_ROW
+  return t;
+}
+constexpr PreBwdForms hgs_pre_bwd_forms = hgs_make_pre_bwd_forms();
+__host__ constexpr bool hgs_pre_bwd_forms_complete() {
+  for (int r = 0; r < HGS_PRE_BWD_ROWS; ++r)
+    if (hgs_pre_bwd_forms.row[r].kernel == nullptr) return false;
+  return true;
+}
+static_assert(hgs_pre_bwd_forms_complete(), "a (filter, mode, degree) combination without a kernel");
+// what the host's launch of a `p` form relies on: a wave per view (64 B threads <= the launch bound <= 1024), and an
+// exchange buffer of (23 + 3 (DEG+1)^2) floats per thread that fits the CU's LDS (160 KB) at the full launch bound
+#define HGS_PRE_BWD_CHECK(DEG, MODE, AA, NAME, THREADS)                                                              \
+  static_assert(MODE != 2 || ((THREADS) % 64 == 0 && (THREADS) <= 1024), #NAME ": a wave per view, <= 1024 threads"); \
+  static_assert(MODE != 2 || (23 + 3 * (DEG + 1) * (DEG + 1)) * (THREADS) * 4 <= 160 * 1024, #NAME ": exchange buffer > LDS");
+HGS_PRE_BWD_FORMS(HGS_PRE_BWD_CHECK)
+#undef HGS_PRE_BWD_CHECK
+}  // namespace
 
 // ------------------------------------------------------------------------- mark visible
 extern "C" __global__ void __launch_bounds__(HGS_BLOCK)

@@ -1,11 +1,11 @@
 """CPU companion of tests/test_gpu_pre_bwd_matrix.py: keeps its case table honest.
 
-1. A restatement of the dispatch rule of the per-Gaussian backward (csrc/api.hip, the `switch` behind
-   HGS_LAUNCH_PRE_BWD; csrc/preprocess.hip: `sh_block_vectorisable`, `hgs_sh_staged`, the `staged` condition of
-   `preprocess_bwd_body`) applied to the table: every launch target, every SH path a target can take, with M == NC and
-   M > NC, and every listed boundary must be hit; a failure names what is missing.  The `switch` has 24 targets that are
-   23 kernels: the loop form at SH degree 3 (`d3`) serves the filter through a run-time bit ("d3+aa" below).  The
-   expectation is for a device that grants the 160 KB dynamic-LDS raise (MI355X).
+1. A restatement of the dispatch rule of the per-Gaussian backward (csrc/api.hip, `backward_impl`'s lookup in
+   `hgs_pre_bwd_forms`; csrc/preprocess.hip: the rows of `HGS_PRE_BWD_FORMS`, `sh_block_vectorisable`, `hgs_sh_staged`,
+   the `staged` condition of `preprocess_bwd_body`) applied to the table: every launch target, every SH path a target can
+   take, with M == NC and M > NC, and every listed boundary must be hit; a failure names what is missing.  The form table
+   has 24 slots that are 23 kernels: the loop form at SH degree 3 (`d3`) serves the filter through a run-time bit
+   ("d3+aa" below).  The expectation is for a device that grants the 160 KB dynamic-LDS raise (MI355X).
 2. The condition behind the GPU module's gate (1e-3 of max|g64|): on every distinct scene of the table (the filter
    included), for every view and for every sum over views the table uses, the fp32 ORACLE is within a quarter of it, and
    at least 90 % of the Gaussians are visible in at least one view.  A condition on the inputs, checked on the reference
