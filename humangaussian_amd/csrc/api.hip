@@ -42,7 +42,7 @@ inline int hgs_knob(const char* name, int dflt) { const char* e = getenv(name); 
 inline int hgs_knob(const char*, int dflt) { return dflt; }
 #endif
 
-#define HGS_CHUNK_ROWS_MIN_VIEWS 3     // calls with at least this many views keep the backward's pair rows chunk-cell-major (binning.hip::hgs_put_pair)
+#define HGS_CHUNK_ROWS_MIN_VIEWS 3     // calls with at least this many views keep the backward's pair rows chunk-cell-major (entryrec.h::hgs_rec_tag)
 #ifndef HGS_PRE_BWD_VPAR_MIN_VIEWS     // (a test build sets it above HGS_MAX_VIEWS: every multi-view call then takes the loop form)
 #define HGS_PRE_BWD_VPAR_MIN_VIEWS 2   // calls with at least this many views run the per-Gaussian backward with one thread per
                                        // (Gaussian, view); fewer: one thread per Gaussian
@@ -505,7 +505,7 @@ int hgs_forward_batch_act_leaf(const hgs_settings* s, int32_t B, int32_t P, int3
     if (entry_capacity > 0 && !bin) return HGS_EINVAL;
     if ((int64_t)B * P >= (1ll << 31) || P >= (1 << 28)) return HGS_EINVAL;
   }
-  // entry ids travel in 27 bits (entpair.x = entry | pairs << 27): a larger list cannot be addressed
+  // entry ids travel in HGS_ENTRY_BITS bits (entpair.x, entryrec.h::hgs_entpair_x): a larger list cannot be addressed
   if (entry_capacity > HGS_MAX_ENTRY_CAPACITY) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DeviceState* const ds = device_state(stream);

@@ -256,16 +256,28 @@ hgs_k_fill_ga(View v, Layout L, hgs_status* __restrict__ status, hgs_status* __r
 // ---------------------------------------------------------------------------- 3. sort
 namespace {
 
-// One (entry, cell) pair of record `rec`: its cell-list element = (record index, id of the pair's gradient row).  Where the
-// blend backward writes the row is a per-call choice (View::pairchunks):
-//  * entry-major ids (1-2 views): the rows of an entry are neighbours, in cell order; the reduction streams the rows of 64
-//    entries as one contiguous block (17 us per view) - the backward pays with isolated 40 B stores (+3 us);
-//  * chunk-cell-major ids (>= 3 views): the rows of every 64-record chunk of the tile list are one block, cell by cell, inside
-//    a cell in list order (hgs_rec_tag): a 16-record batch of the backward writes one or two contiguous runs of rows - with 8
-//    views in flight the isolated stores made it bandwidth-bound (428 -> 273 us) - and the reduction still reads blocks.
-__device__ __forceinline__ void hgs_put_pair(const Layout& L, uint32_t rec, uint32_t row_id, uint32_t slot) {
-  L.cell_list[slot] = make_uint2(rec, row_id);
-}
+// The ONE writer of a list record: the entry of the Gaussian whose GeomRec words are G0 (mx my ca cb), G1 (cc op r g),
+// G2 (b depth rect_lo rect_hi) and OFFSET (its first entry id, relative to CHUNK_BASE), at list position K of the tile.  Computes
+// the entry id (chunk base + the Gaussian's offset + the tile's place in its rect), the cell mask and the folded conic; stores
+// the SortRec - tag word: hgs_rec_tag of the row layout CHUNK_ROWS if the call keeps tags (TAGGED), else 0 - and entpair.x (.y,
+// a pair-row id, follows with the cell lists); leaves the mask in MASK.  Formats: entryrec.h.  Reads L, tx, ty, x0, y0, start and
+// n of the caller.  (A macro: as a __forceinline__ function - pointers and uint4 by value - it changed the code of all four
+// sort kernels, EXPERIMENTS.md.)
+#define HGS_EMIT_RECORD(MASK, G0, G1, G2, OFFSET, CHUNK_BASE, K, TAGGED, CHUNK_ROWS)                                     \
+  {                                                                                                                      \
+    const uint4 g0 = (G0), g1 = (G1), g2 = (G2);                                                                         \
+    const int minx = g2.z & 0xffffu, miny = g2.z >> 16, maxx = g2.w & 0xffffu;                                           \
+    const uint32_t entry = (CHUNK_BASE) + (OFFSET) + (uint32_t)((ty - miny) * (maxx - minx) + (tx - minx));              \
+    const float mx = __uint_as_float(g0.x), my = __uint_as_float(g0.y);                                                  \
+    const float ca = __uint_as_float(g0.z), cb = __uint_as_float(g0.w), cc = __uint_as_float(g1.x);                      \
+    MASK = hgs_cell_mask(mx, my, ca, cb, cc, __uint_as_float(g1.y), x0, y0);                                             \
+    uint4* dst = reinterpret_cast<uint4*>(&L.recs[start + (K)]);                                                         \
+    const float qa = -0.5f * ca * HGS_LOG2E, qb = -cb * HGS_LOG2E, qc = -0.5f * cc * HGS_LOG2E;                          \
+    dst[0] = make_uint4(g0.x, g0.y, __float_as_uint(qa), __float_as_uint(qb));                                           \
+    dst[1] = make_uint4(__float_as_uint(qc), g1.y, g1.z, g1.w);                                                          \
+    dst[2] = make_uint4(g2.x, g2.y, entry, (TAGGED) ? hgs_rec_tag(MASK, (K), n, (CHUNK_ROWS)) : 0u);                     \
+    L.entpair[start + (K)].x = hgs_entpair_x(entry, (uint32_t)__popc(MASK));                                             \
+  }
 
 // Ranges of one tile, from the lengths of its 16 cell lists: pairs (= cell-list slots), cell states, work items.
 // Wave 0 of the workgroup, lane c = cell c.  Two halves: `issue` sends the bump allocation (ONE atomic instruction,
@@ -330,7 +342,7 @@ __device__ __forceinline__ void hgs_alloc_cell_ranges_finish(const View& v, cons
     CellInfo ci;
     ci.base = base; ci.len = len; ci.sbase = sb + a.i_st - a.nst; ci.pbase = pb;
     L.cell_info[(size_t)g * 16 + lane] = ci;
-    const uint32_t key = (uint32_t)g * 16u + (uint32_t)lane;
+    const uint32_t key = hgs_cell_key((uint32_t)g, (uint32_t)lane);
     const size_t dcap = hgs_die_cells(v.TT);
     if (len) L.fwd_cells[((size_t)a.die * HGS_NFC + a.fcls) * dcap + fpos] = key;
     // a work item carries all its wave needs to start: (cell, entries, first cell-list slot, state slot in front of it)
@@ -415,20 +427,7 @@ __device__ __forceinline__ void gather_records(const View& v, const Layout& L, i
       const uint32_t k = kb + (uint32_t)u * nt;
       uint32_t mask = 0;
       if (k < n) {
-        const uint32_t idx = idxv[u];
-        const uint4 g0 = q0[u], g1 = q1[u], g2 = q2[u];
-        // g0: mx my ca cb | g1: cc op r g | g2: b depth rect_lo rect_hi | q3: offset
-        const int minx = g2.z & 0xffffu, miny = g2.z >> 16, maxx = g2.w & 0xffffu;
-        const uint32_t entry = cbase[idx >> 8] + q3[u] + (uint32_t)((ty - miny) * (maxx - minx) + (tx - minx));
-        const float mx = __uint_as_float(g0.x), my = __uint_as_float(g0.y);
-        const float ca = __uint_as_float(g0.z), cb = __uint_as_float(g0.w), cc = __uint_as_float(g1.x);
-        mask = hgs_cell_mask(mx, my, ca, cb, cc, __uint_as_float(g1.y), x0, y0);
-        uint4* dst = reinterpret_cast<uint4*>(&L.recs[start + k]);
-        const float qa = -0.5f * ca * HGS_LOG2E, qb = -cb * HGS_LOG2E, qc = -0.5f * cc * HGS_LOG2E;
-        dst[0] = make_uint4(g0.x, g0.y, __float_as_uint(qa), __float_as_uint(qb));
-        dst[1] = make_uint4(__float_as_uint(qc), g1.y, g1.z, g1.w);
-        dst[2] = make_uint4(g2.x, g2.y, entry, v.pairchunks ? hgs_rec_tag(mask, k, n, false) : 0u);
-        L.entpair[start + k].x = entry | ((uint32_t)__popc(mask) << 27);      // (.y, the first pair id, follows in sweep 2)
+        HGS_EMIT_RECORD(mask, q0[u], q1[u], q2[u], q3[u], cbase[idxv[u] >> 8], k, v.pairchunks, false)      // (entry-major rows; entpair.y follows in sweep 2)
         sorted[k] = (unsigned long long)mask;               // the key is consumed: its slot keeps the mask
       }
 #pragma unroll
@@ -493,7 +492,7 @@ __device__ __forceinline__ void gather_records(const View& v, const Layout& L, i
         if (bit) {
           const uint32_t rank = S.tab[ch][c] + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
           const uint32_t slot = S.cell_base[c] + rank;
-          hgs_put_pair(L, start + k, pair_base + rel + (uint32_t)__popc(mask & ((1u << c) - 1u)), slot);
+          L.cell_list[slot] = make_uint2(start + k, pair_base + rel + (uint32_t)__popc(mask & ((1u << c) - 1u)));
         }
       }
     }
@@ -554,20 +553,7 @@ __device__ __forceinline__ void gather_records_single(const View& v, const Layou
       if (kb0 + (uint32_t)u * nt + (uint32_t)(wv * 64) >= n) continue;       // (wave-uniform) chunk beyond the list
       uint32_t mask = 0;
       if (k < n) {
-        const uint32_t idx = idxv[u];
-        const uint4 g0 = q0[u], g1 = q1[u], g2 = q2[u];
-        // g0: mx my ca cb | g1: cc op r g | g2: b depth rect_lo rect_hi | q3: offset
-        const int minx = g2.z & 0xffffu, miny = g2.z >> 16, maxx = g2.w & 0xffffu;
-        const uint32_t entry = cbase[idx >> 8] + q3[u] + (uint32_t)((ty - miny) * (maxx - minx) + (tx - minx));
-        const float mx = __uint_as_float(g0.x), my = __uint_as_float(g0.y);
-        const float ca = __uint_as_float(g0.z), cb = __uint_as_float(g0.w), cc = __uint_as_float(g1.x);
-        mask = hgs_cell_mask(mx, my, ca, cb, cc, __uint_as_float(g1.y), x0, y0);
-        uint4* dst = reinterpret_cast<uint4*>(&L.recs[start + k]);
-        const float qa = -0.5f * ca * HGS_LOG2E, qb = -cb * HGS_LOG2E, qc = -0.5f * cc * HGS_LOG2E;
-        dst[0] = make_uint4(g0.x, g0.y, __float_as_uint(qa), __float_as_uint(qb));
-        dst[1] = make_uint4(__float_as_uint(qc), g1.y, g1.z, g1.w);
-        dst[2] = make_uint4(g2.x, g2.y, entry, v.pairchunks ? hgs_rec_tag(mask, k, n, false) : 0u);
-        L.entpair[start + k].x = entry | ((uint32_t)__popc(mask) << 27);      // (.y, the first pair id, follows in sweep 2)
+        HGS_EMIT_RECORD(mask, q0[u], q1[u], q2[u], q3[u], cbase[idxv[u] >> 8], k, v.pairchunks, false)      // (entry-major rows; entpair.y follows in sweep 2)
         sorted[k] = (unsigned long long)mask;               // the key is consumed: its slot keeps the mask
       }
       const uint32_t ch = k >> 6;
@@ -644,7 +630,7 @@ __device__ __forceinline__ void gather_records_single(const View& v, const Layou
       mask &= mask - 1u;
       const uint32_t exw = (c < 8) ? (c < 4 ? ex[0] : ex[1]) : (c < 12 ? ex[2] : ex[3]);
       const uint32_t slot = S.cell_base[c] + S.tab[ch][c] + ((exw >> (8 * (c & 3))) & 0xffu);
-      hgs_put_pair(L, start + k, pair_base + rel + r, slot);
+      L.cell_list[slot] = make_uint2(start + k, pair_base + rel + r);
       ++r;
     }
   }
@@ -887,7 +873,7 @@ __device__ __forceinline__ void cell_lists_from_masks(const View& v, const Layou
       if ((mask >> c) & 1u) {
         const uint32_t exc = (ex[c >> 2] >> (8 * (c & 3))) & 0xffu;
         const uint32_t slot = cbase + exc;
-        hgs_put_pair(L, start + k, CH ? rel_chunk + cp + exc : rel + (uint32_t)__popc(mask & ((1u << c) - 1u)), slot);
+        L.cell_list[slot] = make_uint2(start + k, CH ? rel_chunk + cp + exc : rel + (uint32_t)__popc(mask & ((1u << c) - 1u)));
       }
       if (CH) cp += (tot[c >> 2] >> (8 * (c & 3))) & 0xffu;
     }
@@ -1192,19 +1178,8 @@ __device__ __forceinline__ void rank_sort_tile(const View& v, const Layout& L, u
   _Pragma("unroll") for (int u = 0; u < GU; ++u) {                                            \
     if (X##pr[u] != ~0ull) {                                                                  \
       const uint32_t k = (uint32_t)(X##pr[u] >> 32);                                          \
-      const uint4 g0 = X##a[u], g1 = X##b[u], g2 = X##c[u];                                   \
-      /* g0: mx my ca cb | g1: cc op r g | g2: b depth rect_lo rect_hi */                     \
-      const int minx = g2.z & 0xffffu, miny = g2.z >> 16, maxx = g2.w & 0xffffu;              \
-      const uint32_t entry = X##cb[u] + X##off[u] + (uint32_t)((ty - miny) * (maxx - minx) + (tx - minx)); \
-      const float mx = __uint_as_float(g0.x), my = __uint_as_float(g0.y);                     \
-      const float ca = __uint_as_float(g0.z), cb = __uint_as_float(g0.w), cc = __uint_as_float(g1.x); \
-      const uint32_t mask = hgs_cell_mask(mx, my, ca, cb, cc, __uint_as_float(g1.y), x0, y0); \
-      uint4* dst = reinterpret_cast<uint4*>(&L.recs[start + k]);                              \
-      const float qa = -0.5f * ca * HGS_LOG2E, qb = -cb * HGS_LOG2E, qc = -0.5f * cc * HGS_LOG2E; \
-      dst[0] = make_uint4(g0.x, g0.y, __float_as_uint(qa), __float_as_uint(qb));              \
-      dst[1] = make_uint4(__float_as_uint(qc), g1.y, g1.z, g1.w);                             \
-      dst[2] = make_uint4(g2.x, g2.y, entry, CH ? hgs_rec_tag(mask, k, n, true) : 0u);        \
-      L.entpair[start + k].x = entry | ((uint32_t)__popc(mask) << 27);   /* (.y, the first pair id, follows with the lists) */ \
+      uint32_t mask;                                                                          \
+      HGS_EMIT_RECORD(mask, X##a[u], X##b[u], X##c[u], X##off[u], X##cb[u], k, CH, true)   /* (entpair.y follows with the lists) */ \
       masks[k] = (uint16_t)mask;                                                              \
       _Pragma("unroll") for (int wd = 0; wd < 4; ++wd) acc[wd] += hgs_spread4((mask >> (4 * wd)) & 0xfu); \
     }                                                                                         \
@@ -1308,6 +1283,7 @@ __device__ __forceinline__ void sort_rank_body(const View& v, const Layout& L, c
     lds_barrier();                                       // the LDS tables are reused by the next tile
   }
 }
+#undef HGS_EMIT_RECORD
 }  // namespace
 
 static_assert(16 * HGS_SORT_NT >= 4096, "the rank sort takes every list of the LDS class");

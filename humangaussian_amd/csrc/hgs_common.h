@@ -13,6 +13,7 @@
 //   uint32   tile_start[B*T]     first entry    uint2   cell_list[16C] (record index, pair-row id), CELL-major per tile
 //   uint32   tile_order[B*T]     heavy first (+ uint4 tile_rec[B*T]: tile, entries, first entry)
 //                                                   pair-row ids: ENTRY-major (1-2 views) or chunk-cell-major (hgs_rec_tag)
+//   (the packed formats - SortRec with its tag word, entpair.x, the pair-row ids and the cell keys - are defined in entryrec.h)
 //   CellInfo cell_info[B*T][16]  the 16 cell    float   cstate[16C/SEGLEN][6][16]  pixel state every HGS_SEGLEN (128) cell-list entries
 //            lists of a tile                    uint4   items_full[16C/SEGLEN] backward work items (full segments)
 //   uint4    items_part[2][16 B*T] backward work items (last, partial segment of every cell list)
@@ -41,6 +42,7 @@
 
 #include "../../include/hgs_rast.h"
 #include "cellmask.h"
+#include "entryrec.h"   // SortRec + tag, entpair.x, cell keys: the packed formats of the sort stage
 
 #define HGS_TILE 16
 #define HGS_TILE_PIX 256
@@ -48,12 +50,11 @@
 #define HGS_ROW_GROUPS 16      // histogram row groups walked in parallel by hgs_k_tiles (one wave each)
 #define HGS_TILES_PER_WG 64    // tiles per hgs_k_tiles workgroup
 #define HGS_RB 16              // records a row stages per batch (= lanes of a row)
-#define HGS_ROW_F4 (HGS_RB * 3 + 1)   // float4 per staged row: 16 records of 48 B + 16 B, so that the four rows of a wave
+#define HGS_ROW_F4 (HGS_RB * HGS_REC_F4 + 1)   // float4 per staged row: 16 records of 48 B + 16 B, so that the four rows of a wave
                                // (which read four DIFFERENT records per ds_read_b128) sit on different LDS banks
 #define HGS_BWD_BLOCK_WAVES 12 // waves per workgroup of the blend backward: they share one LDS ticket for the workgroup's groups
 #define HGS_SEGLEN 128         // cell-list entries per backward work item; the forward stores the pixel state
                                // of a cell at every multiple of this
-#define HGS_PAIRS_PER_ENTRY 16 // capacity of the pair arrays per entry of capacity (worst case: every cell)
 #define HGS_NEAR_Z 0.2f
 #define HGS_ALPHA_MIN (1.0f / 255.0f)
 #define HGS_ALPHA_MAX 0.99f
@@ -84,25 +85,7 @@ struct __attribute__((aligned(16))) GeomRec {   // 64 B, one per (view, Gaussian
   uint32_t flags;       // bit0: t.x/t.z frustum-clamped, bit1: t.y/t.z clamped
 };
 
-struct __attribute__((aligned(16))) SortRec {   // 48 B, one per (tile, Gaussian) entry
-  float mx, my;         // pixel-space mean
-  float qa, qb, qc;     // conic folded for exp2: qa=-0.5*ca*log2e, qb=-cb*log2e, qc=-0.5*cc*log2e
-  float op, r, g, b, depth;
-  uint32_t entry;       // entry id = chunk base + geom.offset + position of the tile in the rect (< 2^27: HGS_MAX_ENTRY_CAPACITY)
-  uint32_t pad;
-};
 #define HGS_LOG2E 1.4426950408889634f
-// SortRec::pad of the record at list position k of a tile of n entries, written by the sort in calls that keep their pair rows
-// CHUNK-cell-major (View::pairchunks: calls of >= HGS_CHUNK_ROWS_MIN_VIEWS views); both blend kernels overwrite the word with the
-// list position when they gather a record, the pair reduction hgs_k_pair_reduce_ch reads it: the entry's 16-bit cell mask, its
-// place in the 64-record CHUNK of the tile list it belongs to (chunks start at the tile's first record) and the chunk's record
-// count, plus the layout of the chunk's pair rows - bit 28 set: chunk-cell-major (the rows of the chunk are one block starting
-// at entpair.y, cell by cell, inside a cell in list order), clear: entry-major (entpair.y = the entry's first row; the long-list
-// sort classes).  tests/test_pair_rows_cpu.py restates the id arithmetic of both kernels.
-__host__ __device__ __forceinline__ uint32_t hgs_rec_tag(uint32_t mask, uint32_t k, uint32_t n, bool chunk_rows) {
-  const uint32_t left = n - (k & ~63u);
-  return (mask & 0xffffu) | ((k & 63u) << 16) | (((left < 64u ? left : 64u) - 1u) << 22) | (chunk_rows ? 1u << 28 : 0u);
-}
 
 struct __attribute__((aligned(16))) CellInfo {  // one of the 16 cell lists of a tile
   uint32_t base;        // first slot of the list in cell_list (absolute)
@@ -165,13 +148,13 @@ struct Layout {          // pointers carved out of the caller's buffers
   uint32_t* chunk_sums;       // [B*nblk] tiles_touched summed over a 256-Gaussian chunk
   uint32_t* chunk_base;       // [B*nblk] first entry id of the chunk (bump-allocated)
   CellInfo* cell_info;        // [B*T][16]
-  uint32_t* fwd_cells;        // [HGS_NXCD][HGS_NFC][hgs_die_cells]: cell keys (g * 16 + c) of the non-empty cells, per die and length class
+  uint32_t* fwd_cells;        // [HGS_NXCD][HGS_NFC][hgs_die_cells]: cell keys (hgs_cell_key: g * 16 + c) of the non-empty cells, per die and length class
   uint4* items_part;          // [HGS_NXCD][2][hgs_die_cells]: per die, table 0 holds class 1 (from the front) and class 2 (from the back), table 1 class 3
   Counters* ctr;
   unsigned long long* keys;
   SortRec* recs;
   uint2* cell_list;           // [16 C]: (record index, id of the pair's gradient row), cell-major per tile
-  uint2* entpair;             // [C] by record index: (entry id | pairs << 27, first pair row of the entry - or of its chunk, hgs_rec_tag) - what the pair reduction reads
+  uint2* entpair;             // [C] by record index: (hgs_entpair_x: entry id | pairs << HGS_ENTRY_BITS, first pair row of the entry - or of its chunk, hgs_rec_tag) - what the pair reduction reads
   float* cstate;              // [C/4 + 1][6][16]
   uint32_t full_cap;          // slots of ONE die's items_full table (the full segments of all lists would fit in each)
   uint4* items_full;          // [HGS_NXCD][full_cap]: (cell key = g * 16 + c, entries, first cell-list slot, state slot or ~0): all a wave needs to start

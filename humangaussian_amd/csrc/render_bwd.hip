@@ -32,7 +32,7 @@
 // quarters of its 32 cycles multiplied zeros, and the matrix pipe was 40 % of the kernel's issue time.)
 //
 // An (entry, cell) pair row lands at the row id the list element carries (the pair's entry-major id, or its chunk-cell-major
-// id in calls of >= 3 views: binning.hip::hgs_put_pair); hgs_k_pair_reduce_{em,ch} adds the pair rows of
+// id in calls of >= 3 views: entryrec.h::hgs_rec_tag); hgs_k_pair_reduce_{em,ch} adds the pair rows of
 // every entry in cell order (fixed order: no atomics, bitwise reproducible) into one 48 B gradient row per
 // entry, which hgs_k_preprocess_bwd sums per Gaussian.  Pair rows are 40 B (the ten sums, packed).
 //
@@ -154,7 +154,7 @@ hgs_k_render_bwd(View v, Layout L, const hgs_status* __restrict__ status,
     tl_w0 = wall_clock64(); tl_nb = 0; tl_live = 0;
 #endif
     const uint32_t key = item.x, cnt = have ? item.y : 0u;
-    const int g = (int)(key >> 4), c = (int)(key & 15u);
+    const int g = hgs_cell_key_tile(key), c = hgs_cell_key_cell(key);
     const int bview = g / v.T, t_ = g % v.T;
     const int cx0 = (t_ % v.grid_x) * HGS_TILE + (c & 3) * HGS_CELL, cy0 = (t_ / v.grid_x) * HGS_TILE + (c >> 2) * HGS_CELL;
     const int px = cx0 + (i & 3), py = cy0 + (i >> 2);
@@ -171,8 +171,8 @@ hgs_k_render_bwd(View v, Layout L, const hgs_status* __restrict__ status,
     auto list_at = [&](uint32_t e) { return list[(e < cnt) ? e : 0u]; };
     auto gather = [&](const uint2 le, bool valid, float4& r0, float4& r1, float4& r2) {
       const uint32_t idx = valid ? le.x : safe_rec;
-      r0 = recs[3 * (size_t)idx]; r1 = recs[3 * (size_t)idx + 1];
-      const float4 t2 = recs[3 * (size_t)idx + 2];
+      r0 = recs[HGS_REC_F4 * (size_t)idx]; r1 = recs[HGS_REC_F4 * (size_t)idx + 1];
+      const float4 t2 = recs[HGS_REC_F4 * (size_t)idx + 2];
       r2 = make_float4(t2.x, t2.y, t2.z, __uint_as_float(valid ? idx - tstart1 : 0xffffffffu));   // .w: 1-based position in the tile list
     };
     float4 c0, c1, c2;
@@ -367,7 +367,7 @@ hgs_k_render_bwd(View v, Layout L, const hgs_status* __restrict__ status,
       for (int u = 0; u < HGS_RB; u += 2) {
         if (u + 2 < HGS_RB) {
 #pragma unroll
-          for (int m = 0; m < 6; ++m) N[m] = srow[3 * (u + 2) + m];
+          for (int m = 0; m < 6; ++m) N[m] = srow[HGS_REC_F4 * (u + 2) + m];
         }
         __builtin_amdgcn_sched_barrier(0x7f);       // LDS reads stay ahead of the evaluation (the scheduler would sink them to their use)
         eval_pair(u, P[0], P[1], P[2], P[3], P[4], P[5]);
@@ -422,6 +422,76 @@ hgs_k_render_bwd(View v, Layout L, const hgs_status* __restrict__ status,
   }
 }
 
+#define HGS_RED_ROWS 128
+#define HGS_RED_RUNS 4      // contiguous runs a wave streams before its lanes fall back to gathering their own rows
+static_assert(HGS_RED_ROWS * HGS_PROW_F2 == 10 * 64, "ten float2 per lane and window");
+
+namespace {
+
+// ---- the streaming core both reductions share: a block of `total` contiguous pair rows behind SRC goes through the wave's LDS
+// slice in windows of HGS_RED_ROWS rows, double buffered through ten registers per lane (b0 .. b9 - named registers: an array
+// here went to scratch memory): the loads of window t + 1 are in flight while window t is summed (a wave has ~3 windows; one
+// after the other their load latency was most of the kernel's 20 us).
+// HGS_RED_ISSUE: the loads of the window at row T0 into b0 .. b9 (reads `lane` and `total` of the caller).  No branch around
+// the loads: behind the last window every lane re-reads element 0 - one cache line; a conditional block made the compiler
+// wait for the loads where they are issued.
+#define HGS_RED_ISSUE(SRC, T0)                                                                                 \
+  {                                                                                                            \
+    const uint32_t t0n__ = (T0);                                                                               \
+    const bool any__ = t0n__ < total;                                                                          \
+    const uint32_t last__ = any__ ? min((uint32_t)HGS_RED_ROWS, total - t0n__) * HGS_PROW_F2 - 1u : 0u;        \
+    const float2* p__ = (SRC) + (any__ ? (size_t)t0n__ * HGS_PROW_F2 : 0);                                     \
+    b0 = p__[min((uint32_t)lane, last__)];        b1 = p__[min((uint32_t)lane + 64u, last__)];                 \
+    b2 = p__[min((uint32_t)lane + 128u, last__)]; b3 = p__[min((uint32_t)lane + 192u, last__)];                \
+    b4 = p__[min((uint32_t)lane + 256u, last__)]; b5 = p__[min((uint32_t)lane + 320u, last__)];                \
+    b6 = p__[min((uint32_t)lane + 384u, last__)]; b7 = p__[min((uint32_t)lane + 448u, last__)];                \
+    b8 = p__[min((uint32_t)lane + 512u, last__)]; b9 = p__[min((uint32_t)lane + 576u, last__)];                \
+  }
+
+// HGS_RED_STORE_WINDOW: the window in b0 .. b9 (`nfl` float2 of it are rows) -> the wave's LDS slice `sl`.
+// HGS_ADD_PAIR_ROW: one pair row (five float2 at Q, LDS or HBM) added to the entry's ten sums s0 .. s4.
+// (Macros: as functions - the registers by value, the sums by reference - both changed the register allocation of
+//  hgs_k_pair_reduce_ch, EXPERIMENTS.md.)
+#define HGS_RED_STORE_WINDOW()                                                                                 \
+  {                                                                                                            \
+    if ((uint32_t)lane < nfl) sl[lane] = b0;              if ((uint32_t)lane + 64u < nfl) sl[lane + 64] = b1;   \
+    if ((uint32_t)lane + 128u < nfl) sl[lane + 128] = b2; if ((uint32_t)lane + 192u < nfl) sl[lane + 192] = b3; \
+    if ((uint32_t)lane + 256u < nfl) sl[lane + 256] = b4; if ((uint32_t)lane + 320u < nfl) sl[lane + 320] = b5; \
+    if ((uint32_t)lane + 384u < nfl) sl[lane + 384] = b6; if ((uint32_t)lane + 448u < nfl) sl[lane + 448] = b7; \
+    if ((uint32_t)lane + 512u < nfl) sl[lane + 512] = b8; if ((uint32_t)lane + 576u < nfl) sl[lane + 576] = b9; \
+  }
+#define HGS_ADD_PAIR_ROW(Q)                                                                                    \
+  {                                                                                                            \
+    const float2* q__ = (Q);                                                                                   \
+    const float2 a0 = q__[0], a1 = q__[1], a2 = q__[2], a3 = q__[3], a4 = q__[4];                              \
+    s0.x += a0.x; s0.y += a0.y; s1.x += a1.x; s1.y += a1.y; s2.x += a2.x; s2.y += a2.y;                        \
+    s3.x += a3.x; s3.y += a3.y; s4.x += a4.x; s4.y += a4.y;                                                    \
+  }
+
+// the entry's gradient row (48 B: the ten sums + 8 B of zeros); `poisoned` (more pairs than the scratch was sized for -
+// hgs_k_render_bwd wrote none, no row was read): NaN, loud and in bounds
+__device__ __forceinline__ void hgs_store_grad_row(float* __restrict__ grad_rows, uint32_t entry, bool poisoned, float2 s0, float2 s1,
+                                                   float2 s2, float2 s3, float2 s4) {
+  if (poisoned) s0.x = s0.y = s1.x = s1.y = s2.x = s2.y = s3.x = s3.y = s4.x = s4.y = __builtin_nanf("");
+  float4* dst = reinterpret_cast<float4*>(grad_rows + (size_t)entry * HGS_ROW_FLOATS);
+  dst[0] = make_float4(s0.x, s0.y, s1.x, s1.y); dst[1] = make_float4(s2.x, s2.y, s3.x, s3.y);
+  dst[2] = make_float4(s4.x, s4.y, 0.0f, 0.0f);
+}
+
+// Entries of the call.  R_host: the entry count of a caller that holds the forward's status (hgs_backward* refuses an
+// overflowed one on the host): the kernel's first loads then do not wait for a status round trip (~1.5 us in front of every
+// wave's chain entpair -> rows); ~0: unknown, read the device copy (false: the forward overflowed, nothing to reduce)
+__device__ __forceinline__ bool hgs_red_entries(const hgs_status* __restrict__ status, uint32_t R_host, uint32_t& R) {
+  R = R_host;
+  if (R_host == 0xffffffffu) {
+    if (status->overflow) return false;
+    R = status->num_rendered;
+  }
+  return true;
+}
+
+}  // namespace
+
 // ------------------------------------------------------------------------------ pair reduction, ENTRY-major rows (calls of 1-2 views)
 // One gradient row per tile entry = the sum of the entry's (entry, cell) pair rows, cells in ascending order
 // (deterministic).  A wave64 takes 64 consecutive entries; pair ids are entry-major, so their pair rows are ONE
@@ -429,30 +499,22 @@ hgs_k_render_bwd(View v, Layout L, const hgs_status* __restrict__ status,
 // time, and every lane (= entry) then adds its own rows from LDS in order.  (Per-thread row loads - 48 B at a
 // stride of ~170 B per lane - reached 3 TB/s; at 8 views the 456 MB of pair rows made this the second-largest
 // kernel of the step.)  A wave whose entries straddle tiles (pair ranges apart) streams one run per tile.
-#define HGS_RED_ROWS 128
-#define HGS_RED_RUNS 4      // contiguous runs a wave streams before its lanes fall back to gathering their own rows
 extern "C" __global__ void __launch_bounds__(256)
 hgs_k_pair_reduce_em(View v, Layout L, const hgs_status* __restrict__ status, const SortRec* __restrict__ recs_all,
                   const float* __restrict__ pair_rows, float* __restrict__ grad_rows, uint32_t pair_cap, uint32_t R_host) {
   __shared__ float2 s_rows[4][HGS_RED_ROWS * HGS_PROW_F2];
-  // R_host: the entry count of a caller that holds the forward's status (hgs_backward* refuses an overflowed one on the
-  // host): the kernel's first loads then do not wait for a status round trip (~1.5 us in front of every wave's chain
-  // entpair -> rows); ~0: unknown, read the device copy
-  uint32_t R = R_host;
-  if (R_host == 0xffffffffu) {
-    if (status->overflow) return;
-    R = status->num_rendered;
-  }
+  uint32_t R;
+  if (!hgs_red_entries(status, R_host, R)) return;
   const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p - (uint32_t)lane >= R) return;                       // (wave-uniform)
   const bool have = p < R;
   uint2 ep = make_uint2(0u, 0u);
-  if (have) ep = L.entpair[p];                                // entry id | pairs << 27, first pair id
-  const uint32_t entry = ep.x & 0x7ffffffu;
+  if (have) ep = L.entpair[p];                                // hgs_entpair_x, first pair id
+  const uint32_t entry = hgs_entpair_entry(ep.x);
   // more pairs than the scratch was sized for (hgs_k_render_bwd wrote none): no row is read, the gradient rows are NaN
   const bool poisoned = (uint32_t)L.ctr->alloc_ps > pair_cap;
-  const uint32_t cnt = poisoned ? 0u : ep.x >> 27;
+  const uint32_t cnt = poisoned ? 0u : hgs_entpair_pairs(ep.x);
   const uint32_t incl = hgs_wave_incl_scan(cnt), off = incl - cnt;
   float2 s0 = make_float2(0.f, 0.f), s1 = s0, s2 = s0, s3 = s0, s4 = s0;
   // RUNS of contiguous rows: inside a tile the pair ids are entry-major, so the rows of the wave's entries of ONE tile are one
@@ -476,70 +538,28 @@ hgs_k_pair_reduce_em(View v, Layout L, const hgs_status* __restrict__ status, co
     const uint32_t total = r_hi - r_lo;
     const uint32_t moff = off - r_lo, mcnt = mine ? cnt : 0u;               // this lane's rows inside the run (moff wraps for lanes outside: mcnt = 0)
     const float2* __restrict__ src = reinterpret_cast<const float2*>(pair_rows) + (size_t)(base + r_lo) * HGS_PROW_F2;
-    // double buffered through registers: the loads of tile t + 1 are in flight while tile t is summed (a wave has
-    // ~3 tiles; one after the other their load latency was most of the kernel's 20 us)
-    static_assert(HGS_RED_ROWS * HGS_PROW_F2 == 10 * 64, "ten float2 per lane and tile");
-    float2 b0, b1, b2, b3, b4, b5, b6, b7, b8, b9;   // (named registers: an array here went to scratch memory)
-    // (no branch around the loads: behind the last tile every lane re-reads element 0 - one cache line; a
-    // conditional block made the compiler wait for the loads where they are issued)
-#define HGS_RED_ISSUE(T0)                                                                                      \
-  {                                                                                                            \
-    const uint32_t t0n__ = (T0);                                                                               \
-    const bool any__ = t0n__ < total;                                                                          \
-    const uint32_t last__ = any__ ? min((uint32_t)HGS_RED_ROWS, total - t0n__) * HGS_PROW_F2 - 1u : 0u;        \
-    const float2* p__ = src + (any__ ? (size_t)t0n__ * HGS_PROW_F2 : 0);                                       \
-    b0 = p__[min((uint32_t)lane, last__)];        b1 = p__[min((uint32_t)lane + 64u, last__)];                 \
-    b2 = p__[min((uint32_t)lane + 128u, last__)]; b3 = p__[min((uint32_t)lane + 192u, last__)];                \
-    b4 = p__[min((uint32_t)lane + 256u, last__)]; b5 = p__[min((uint32_t)lane + 320u, last__)];                \
-    b6 = p__[min((uint32_t)lane + 384u, last__)]; b7 = p__[min((uint32_t)lane + 448u, last__)];                \
-    b8 = p__[min((uint32_t)lane + 512u, last__)]; b9 = p__[min((uint32_t)lane + 576u, last__)];                \
-  }
-    HGS_RED_ISSUE(0u);
+    float2 b0, b1, b2, b3, b4, b5, b6, b7, b8, b9;
+    HGS_RED_ISSUE(src, 0u);
     for (uint32_t t0 = 0; t0 < total; t0 += HGS_RED_ROWS) {
       const uint32_t nrow = min((uint32_t)HGS_RED_ROWS, total - t0);
       const uint32_t nfl = nrow * HGS_PROW_F2;
       __builtin_amdgcn_wave_barrier();               // the previous tile's LDS reads are done
-      if ((uint32_t)lane < nfl) sl[lane] = b0;
-      if ((uint32_t)lane + 64u < nfl) sl[lane + 64] = b1;
-      if ((uint32_t)lane + 128u < nfl) sl[lane + 128] = b2;
-      if ((uint32_t)lane + 192u < nfl) sl[lane + 192] = b3;
-      if ((uint32_t)lane + 256u < nfl) sl[lane + 256] = b4;
-      if ((uint32_t)lane + 320u < nfl) sl[lane + 320] = b5;
-      if ((uint32_t)lane + 384u < nfl) sl[lane + 384] = b6;
-      if ((uint32_t)lane + 448u < nfl) sl[lane + 448] = b7;
-      if ((uint32_t)lane + 512u < nfl) sl[lane + 512] = b8;
-      if ((uint32_t)lane + 576u < nfl) sl[lane + 576] = b9;
-      HGS_RED_ISSUE(t0 + HGS_RED_ROWS);
+      HGS_RED_STORE_WINDOW()
+      HGS_RED_ISSUE(src, t0 + HGS_RED_ROWS);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       if (mcnt) {
         const uint32_t r_begin = max(moff, t0), r_end = min(moff + mcnt, t0 + nrow);
-        for (uint32_t r = r_begin; r < r_end; ++r) {
-          const float2* q = sl + HGS_PROW_F2 * (r - t0);
-          const float2 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4];
-          s0.x += a0.x; s0.y += a0.y; s1.x += a1.x; s1.y += a1.y; s2.x += a2.x; s2.y += a2.y;
-          s3.x += a3.x; s3.y += a3.y; s4.x += a4.x; s4.y += a4.y;
-        }
+        for (uint32_t r = r_begin; r < r_end; ++r) HGS_ADD_PAIR_ROW(sl + HGS_PROW_F2 * (r - t0))
       }
     }
-#undef HGS_RED_ISSUE
   }
   if (todo != 0ull) {
     const bool left = ((todo >> lane) & 1ull) != 0ull;
     const float2* __restrict__ rows = reinterpret_cast<const float2*>(pair_rows) + (size_t)ep.y * HGS_PROW_F2;
-    for (uint32_t r = 0; r < (left ? cnt : 0u); ++r) {
-      const float2* q = rows + HGS_PROW_F2 * r;
-      const float2 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4];
-      s0.x += a0.x; s0.y += a0.y; s1.x += a1.x; s1.y += a1.y; s2.x += a2.x; s2.y += a2.y;
-      s3.x += a3.x; s3.y += a3.y; s4.x += a4.x; s4.y += a4.y;
-    }
+    for (uint32_t r = 0; r < (left ? cnt : 0u); ++r) HGS_ADD_PAIR_ROW(rows + HGS_PROW_F2 * r)
   }
-  if (have) {
-    if (poisoned) s0.x = s0.y = s1.x = s1.y = s2.x = s2.y = s3.x = s3.y = s4.x = s4.y = __builtin_nanf("");
-    float4* dst = reinterpret_cast<float4*>(grad_rows + (size_t)entry * HGS_ROW_FLOATS);
-    dst[0] = make_float4(s0.x, s0.y, s1.x, s1.y); dst[1] = make_float4(s2.x, s2.y, s3.x, s3.y);
-    dst[2] = make_float4(s4.x, s4.y, 0.0f, 0.0f);
-  }
+  if (have) hgs_store_grad_row(grad_rows, entry, poisoned, s0, s1, s2, s3, s4);
 }
 
 // ------------------------------------------------------------------------------ pair reduction, CHUNK-cell-major rows (calls of >= 3 views)
@@ -562,27 +582,24 @@ extern "C" __global__ void __launch_bounds__(256)
 hgs_k_pair_reduce_ch(View v, Layout L, const hgs_status* __restrict__ status, const SortRec* __restrict__ recs_all,
                       const float* __restrict__ pair_rows, float* __restrict__ grad_rows, uint32_t pair_cap, uint32_t R_host) {
   __shared__ float2 s_rows[4][HGS_RED_ROWS * HGS_PROW_F2];
-  uint32_t R = R_host;                                     // (see hgs_k_pair_reduce_em)
-  if (R_host == 0xffffffffu) {
-    if (status->overflow) return;
-    R = status->num_rendered;
-  }
+  uint32_t R;
+  if (!hgs_red_entries(status, R_host, R)) return;
   const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
   const uint32_t w0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;      // the wave's window of records
   if (w0 >= R) return;                                                   // (wave-uniform)
-  const uint32_t* __restrict__ tags = reinterpret_cast<const uint32_t*>(recs_all) + 11;      // SortRec::pad
+  const uint32_t* __restrict__ tags = reinterpret_cast<const uint32_t*>(recs_all) + HGS_REC_TAG_WORD;      // SortRec::tag
   const uint32_t pa = w0 + (uint32_t)lane;
   const uint32_t qa = min(pa, R - 1u), qb = min(pa + 64u, R - 1u);
-  const uint32_t tagA = tags[(size_t)qa * 12u], tagB = tags[(size_t)qb * 12u];
+  const uint32_t tagA = tags[(size_t)qa * HGS_REC_WORDS], tagB = tags[(size_t)qb * HGS_REC_WORDS];
   const uint2 epA = L.entpair[qa], epB = L.entpair[qb];
   float2* __restrict__ sl = s_rows[w];
-  unsigned long long starts = __ballot(pa < R && ((tagA >> 16) & 63u) == 0u);
+  unsigned long long starts = __ballot(pa < R && hgs_tag_pos(tagA) == 0u);
   while (starts) {                                                        // (wave-uniform)
     const int s = (int)__builtin_ctzll(starts);
     starts &= starts - 1ull;
     const uint32_t t_s = (uint32_t)__builtin_amdgcn_readlane((int)tagA, s);
-    const uint32_t C = ((t_s >> 22) & 63u) + 1u;
-    const bool chunk_rows = ((t_s >> 28) & 1u) != 0u;
+    const uint32_t C = hgs_tag_count(t_s);
+    const bool chunk_rows = hgs_tag_chunk_rows(t_s);
     const bool have = (uint32_t)lane < C;
     const int src = (s + lane) & 63;
     const bool from_b = s + lane >= 64;
@@ -592,8 +609,8 @@ hgs_k_pair_reduce_ch(View v, Layout L, const hgs_status* __restrict__ status, co
     const uint32_t tag = from_b ? tB : tA, epx = from_b ? xB : xA, epy = from_b ? yB : yA;
     // (more pairs than the scratch was sized for - hgs_k_render_bwd wrote none: no row is read, the gradient rows are NaN)
     const bool poisoned = (uint32_t)L.ctr->alloc_ps > pair_cap;
-    const uint32_t mask = (have && !poisoned) ? (tag & 0xffffu) : 0u;
-    const uint32_t entry = epx & 0x7ffffffu, cnt = (have && !poisoned) ? (epx >> 27) : 0u;
+    const uint32_t mask = (have && !poisoned) ? hgs_tag_mask(tag) : 0u;
+    const uint32_t entry = hgs_entpair_entry(epx), cnt = (have && !poisoned) ? hgs_entpair_pairs(epx) : 0u;
     float2 s0 = make_float2(0.f, 0.f), s1 = s0, s2 = s0, s3 = s0, s4 = s0;
     if (chunk_rows) {
       // block positions of this lane's rows, per cell; cells' first positions and sizes (wave-uniform)
@@ -609,54 +626,26 @@ hgs_k_pair_reduce_ch(View v, Layout L, const hgs_status* __restrict__ status, co
       }
       const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)epy, 0);       // the chunk's first row (the same in all its lanes)
       const float2* __restrict__ srcp = reinterpret_cast<const float2*>(pair_rows) + (size_t)base * HGS_PROW_F2;
-      static_assert(HGS_RED_ROWS * HGS_PROW_F2 == 10 * 64, "ten float2 per lane and window");
       float2 b0, b1, b2, b3, b4, b5, b6, b7, b8, b9;
-#define HGS_REDL_ISSUE(T0)                                                                                     \
-  {                                                                                                            \
-    const uint32_t t0n__ = (T0);                                                                               \
-    const bool any__ = t0n__ < total;                                                                          \
-    const uint32_t last__ = any__ ? min((uint32_t)HGS_RED_ROWS, total - t0n__) * HGS_PROW_F2 - 1u : 0u;        \
-    const float2* p__ = srcp + (any__ ? (size_t)t0n__ * HGS_PROW_F2 : 0);                                      \
-    b0 = p__[min((uint32_t)lane, last__)];        b1 = p__[min((uint32_t)lane + 64u, last__)];                 \
-    b2 = p__[min((uint32_t)lane + 128u, last__)]; b3 = p__[min((uint32_t)lane + 192u, last__)];                \
-    b4 = p__[min((uint32_t)lane + 256u, last__)]; b5 = p__[min((uint32_t)lane + 320u, last__)];                \
-    b6 = p__[min((uint32_t)lane + 384u, last__)]; b7 = p__[min((uint32_t)lane + 448u, last__)];                \
-    b8 = p__[min((uint32_t)lane + 512u, last__)]; b9 = p__[min((uint32_t)lane + 576u, last__)];                \
-  }
       if (total) {
-        HGS_REDL_ISSUE(0u);
+        HGS_RED_ISSUE(srcp, 0u);
         for (uint32_t t0 = 0; t0 < total; t0 += HGS_RED_ROWS) {
           const uint32_t nrow = min((uint32_t)HGS_RED_ROWS, total - t0);
           const uint32_t nfl = nrow * HGS_PROW_F2;
           __builtin_amdgcn_wave_barrier();             // the previous window's LDS reads are done
-          if ((uint32_t)lane < nfl) sl[lane] = b0;
-          if ((uint32_t)lane + 64u < nfl) sl[lane + 64] = b1;
-          if ((uint32_t)lane + 128u < nfl) sl[lane + 128] = b2;
-          if ((uint32_t)lane + 192u < nfl) sl[lane + 192] = b3;
-          if ((uint32_t)lane + 256u < nfl) sl[lane + 256] = b4;
-          if ((uint32_t)lane + 320u < nfl) sl[lane + 320] = b5;
-          if ((uint32_t)lane + 384u < nfl) sl[lane + 384] = b6;
-          if ((uint32_t)lane + 448u < nfl) sl[lane + 448] = b7;
-          if ((uint32_t)lane + 512u < nfl) sl[lane + 512] = b8;
-          if ((uint32_t)lane + 576u < nfl) sl[lane + 576] = b9;
-          HGS_REDL_ISSUE(t0 + HGS_RED_ROWS);
+          HGS_RED_STORE_WINDOW()
+          HGS_RED_ISSUE(srcp, t0 + HGS_RED_ROWS);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
 #pragma unroll
           for (int c = 0; c < 16; ++c) {
             if (cp0[c] < t0 + nrow && cp0[c] + ncell[c] > t0) {          // (wave-uniform: the cell has rows in this window)
               const uint32_t r = rel[c] - t0;                            // (wraps for rows of earlier windows: the range test drops them)
-              if (((mask >> c) & 1u) && r < nrow) {
-                const float2* q = sl + HGS_PROW_F2 * r;
-                const float2 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4];
-                s0.x += a0.x; s0.y += a0.y; s1.x += a1.x; s1.y += a1.y; s2.x += a2.x; s2.y += a2.y;
-                s3.x += a3.x; s3.y += a3.y; s4.x += a4.x; s4.y += a4.y;
-              }
+              if (((mask >> c) & 1u) && r < nrow) HGS_ADD_PAIR_ROW(sl + HGS_PROW_F2 * r)
             }
           }
         }
       }
-#undef HGS_REDL_ISSUE
     } else {
       // chunks of the long-list sort classes: entry-major rows, gathered (16 + 16 + 8 B loads at 8 B alignment)
       for (uint32_t j = 0; j < 16u; ++j) {
@@ -672,11 +661,9 @@ hgs_k_pair_reduce_ch(View v, Layout L, const hgs_status* __restrict__ status, co
         }
       }
     }
-    if (have) {
-      if (poisoned) s0.x = s0.y = s1.x = s1.y = s2.x = s2.y = s3.x = s3.y = s4.x = s4.y = __builtin_nanf("");
-      float4* dst = reinterpret_cast<float4*>(grad_rows + (size_t)entry * HGS_ROW_FLOATS);
-      dst[0] = make_float4(s0.x, s0.y, s1.x, s1.y); dst[1] = make_float4(s2.x, s2.y, s3.x, s3.y);
-      dst[2] = make_float4(s4.x, s4.y, 0.0f, 0.0f);
-    }
+    if (have) hgs_store_grad_row(grad_rows, entry, poisoned, s0, s1, s2, s3, s4);
   }
 }
+#undef HGS_RED_ISSUE
+#undef HGS_RED_STORE_WINDOW
+#undef HGS_ADD_PAIR_ROW

@@ -107,7 +107,7 @@ __device__ __forceinline__ void render_fwd_cell4(const View& v, const Layout& L,
                                                  float* __restrict__ out_alpha, float4* __restrict__ s_rec_w) {
   const int lane = (int)threadIdx.x & 63;
   const int r = lane >> 4, i = lane & 15;
-  const int g = (int)(key >> 4), c = (int)(key & 15u);
+  const int g = hgs_cell_key_tile(key), c = hgs_cell_key_cell(key);
   const int bview = g / v.T, t = g % v.T;
   const size_t HW = (size_t)v.H * v.W;
   const int px = (t % v.grid_x) * HGS_TILE + (c & 3) * HGS_CELL + (i & 3);
@@ -132,8 +132,8 @@ __device__ __forceinline__ void render_fwd_cell4(const View& v, const Layout& L,
   auto load_idx = [&](uint32_t e) { return list[(e < len) ? e : 0u].x; };
   auto gather = [&](uint32_t idx_raw, bool valid, float4& r0, float4& r1, float4& r2) {
     const uint32_t idx = valid ? idx_raw : tstart1 + 1u;               // (the tile's first record)
-    r0 = recs[3 * (size_t)idx]; r1 = recs[3 * (size_t)idx + 1];
-    const float4 t2 = recs[3 * (size_t)idx + 2];
+    r0 = recs[HGS_REC_F4 * (size_t)idx]; r1 = recs[HGS_REC_F4 * (size_t)idx + 1];
+    const float4 t2 = recs[HGS_REC_F4 * (size_t)idx + 2];
     r2 = make_float4(t2.x, t2.y, t2.z, __uint_as_float(valid ? idx - tstart1 : 0xffffffffu));
   };
   // blocks of 64 records, one per lane; indices two and three blocks ahead, records one block ahead
@@ -153,18 +153,18 @@ __device__ __forceinline__ void render_fwd_cell4(const View& v, const Layout& L,
     }
     __builtin_amdgcn_wave_barrier();                 // the previous block's LDS reads are done
     c1.y = (__float_as_uint(c2.w) == 0xffffffffu) ? 0.0f : c1.y;      // pad record: never blends
-    s_rec_w[3 * lane + 0] = c0; s_rec_w[3 * lane + 1] = c1; s_rec_w[3 * lane + 2] = c2;
+    s_rec_w[HGS_REC_F4 * lane + 0] = c0; s_rec_w[HGS_REC_F4 * lane + 1] = c1; s_rec_w[HGS_REC_F4 * lane + 2] = c2;
     const uint32_t idx_n = load_idx(it0 + 192u + (uint32_t)lane);
     gather(idx_a, it0 + 64u + (uint32_t)lane < len, c0, c1, c2);
     idx_a = idx_b; idx_b = idx_n;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const float4* __restrict__ myrec = s_rec_w + 3 * r;          // record 4 k + r of the block
+    const float4* __restrict__ myrec = s_rec_w + HGS_REC_F4 * r;          // record 4 k + r of the block
     float4 ra = myrec[0], rb = myrec[1], rc = myrec[2];
 #pragma unroll 2
     for (int k = 0; k < 16; ++k) {
       float4 na = zero4, nb = zero4, nc = zero4;
-      if (k + 1 < 16) { na = myrec[12 * (k + 1) + 0]; nb = myrec[12 * (k + 1) + 1]; nc = myrec[12 * (k + 1) + 2]; }
+      if (k + 1 < 16) { na = myrec[4 * HGS_REC_F4 * (k + 1) + 0]; nb = myrec[4 * HGS_REC_F4 * (k + 1) + 1]; nc = myrec[4 * HGS_REC_F4 * (k + 1) + 2]; }
       __builtin_amdgcn_sched_barrier(0x7f);
       float G, alpha, m2, m3;
       const bool keep = hgs_eval_alpha(ra.x - pxf, ra.y - pyf, ra.z, ra.w, rb.x, rb.y, G, alpha, m2, m3);
@@ -269,7 +269,7 @@ __device__ __forceinline__ void render_fwd_cells(const View& v, const Layout& L,
     const uint32_t k_ = fwd_cell_key(L, hgs_die_cells(v.TT), pre, have ? mycls : HGS_FWD_C4, have ? q : 0u);
     key = have ? k_ : 0u;
   }
-  const int g = (int)(key >> 4), c = (int)(key & 15u);
+  const int g = hgs_cell_key_tile(key), c = hgs_cell_key_cell(key);
   const int bview = g / v.T, t = g % v.T;
   const size_t HW = (size_t)v.H * v.W;
   const int px = (t % v.grid_x) * HGS_TILE + (c & 3) * HGS_CELL + (i & 3);
@@ -301,8 +301,8 @@ __device__ __forceinline__ void render_fwd_cells(const View& v, const Layout& L,
   auto load_idx = [&](uint32_t e) { return list[(e < len) ? e : 0u].x; };
   auto gather = [&](uint32_t idx_raw, bool valid, float4& r0, float4& r1, float4& r2) {
     const uint32_t idx = valid ? idx_raw : safe_rec;
-    r0 = recs[3 * (size_t)idx]; r1 = recs[3 * (size_t)idx + 1];
-    const float4 t2 = recs[3 * (size_t)idx + 2];
+    r0 = recs[HGS_REC_F4 * (size_t)idx]; r1 = recs[HGS_REC_F4 * (size_t)idx + 1];
+    const float4 t2 = recs[HGS_REC_F4 * (size_t)idx + 2];
     r2 = make_float4(t2.x, t2.y, t2.z, __uint_as_float(valid ? idx - tstart1 : 0xffffffffu));
   };
   float4 c0, c1, c2, d0, d1, d2;                    // records of batch b (c) and b + 1 (d)
@@ -348,7 +348,7 @@ __device__ __forceinline__ void render_fwd_cells(const View& v, const Layout& L,
     for (int u0 = 0; u0 < HGS_RB; u0 += 2) {
       if (u0 + 2 < HGS_RB) {
 #pragma unroll
-        for (int m = 0; m < 6; ++m) N[m] = srow[3 * (u0 + 2) + m];
+        for (int m = 0; m < 6; ++m) N[m] = srow[HGS_REC_F4 * (u0 + 2) + m];
       }
       // the machine scheduler would sink those reads to their first use (and expose one LDS round trip per pair):
       // LDS instructions may not cross this point, everything else may

@@ -1,8 +1,20 @@
-"""Do A/B builds of the library give the same bits?  Forward + backward through the raw ABI on two scenes (a small
-cloud with lists > 1024 entries: segments, transmittance products; a wider one), fingerprint of every output and
-of the saved state, for the in-tree build and every library given on the command line:
-  python tools/cmp_variant.py variants/X/libhgs_rast.so [...]            (on the GPU box)"""
+"""Do A/B builds of the library give the same bits?  Fingerprints (sha1 of every output, of the saved state and of every
+gradient) of
+  * forward + backward through the raw ABI on two single-view scenes (a small cloud with lists > 1024 entries: segments,
+    transmittance products; a wider one), and
+  * one batched call of 3 views of the small cloud through rasterize_gaussians_batch, forward + backward: the path of
+    calls of >= 3 views (hgs_k_sort_lds_ch, chunk-cell-major pair rows, hgs_k_pair_reduce_ch) that no single-view call takes.
+
+  python tools/cmp_variant.py variants/X/libhgs_rast.so [...]   raw-ABI cases: the in-tree build against every library given
+  python tools/cmp_variant.py --save FILE                       all cases of THIS tree's build -> FILE (json)
+  python tools/cmp_variant.py --against FILE                    all cases of this tree's build compared with a saved FILE
+
+The torch binding finds its library by rpath, so the batched case cannot be pointed at another library inside one process:
+build the other commit in its own checkout, --save there, --against here (each run a fresh process).  (On the GPU box.)"""
+import argparse
 import hashlib
+import json
+import math
 import os
 import sys
 
@@ -13,6 +25,8 @@ from abi_runner import RawCall
 from helpers import make_scene
 from humangaussian_amd import _lib
 
+LONG = dict(P=2600, H=32, W=32, spread=0.02, scale=0.01, dist=2.0)
+
 
 def h(t):
     return hashlib.sha1(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:12]
@@ -20,7 +34,7 @@ def h(t):
 
 def fingerprint():
     out = []
-    for name, kw, op in (("long", dict(P=2600, seed=77, H=32, W=32, spread=0.02, scale=0.01, dist=2.0), 0.03),
+    for name, kw, op in (("long", dict(seed=77, **LONG), 0.03),
                          ("wide", dict(P=6000, seed=5, H=128, W=160, spread=0.3, scale=0.05), None)):
         sc = make_scene(**kw)
         if op is not None:
@@ -36,19 +50,66 @@ def fingerprint():
     return out
 
 
-ref = fingerprint()
-for r in ref:
-    print("in-tree", r)
-same = True
-for path in sys.argv[1:]:
-    _lib._lib = None
-    _lib.LIB_PATH = os.path.abspath(path)
-    got = fingerprint()
+def fingerprint_batch():
+    """3 views of the "long" cloud in one call (cameras of make_scene seeds 77, 78, 79), every view with its own gradients"""
+    from humangaussian_amd import GaussianRasterizationSettings, rasterize_gaussians_batch
+    dev = "cuda"
+    sc = make_scene(seed=77, **LONG)
+    sc["opacities"] = torch.full_like(sc["opacities"], 0.03)
+    cams = [make_scene(seed=s, **LONG)["cam"] for s in (77, 78, 79)]
+    rsl = [GaussianRasterizationSettings(c.image_height, c.image_width, math.tan(c.FoVx * 0.5), math.tan(c.FoVy * 0.5),
+                                         sc["bg"].to(dev), 1.0, c.world_view_transform.to(dev), c.full_proj_transform.to(dev),
+                                         sc["sh_degree"], c.camera_center.to(dev), False, False) for c in cams]
+    names = ("means3D", "shs", "opacities", "scales", "rotations")
+    ins = {k: sc[k].to(dev).requires_grad_(True) for k in names}
+    B, P, H, W = len(cams), LONG["P"], LONG["H"], LONG["W"]
+    m2 = torch.zeros(B, P, 3, device=dev, requires_grad=True)
+    c, r, d, a = rasterize_gaussians_batch(ins["means3D"], m2, ins["shs"], None, ins["opacities"], ins["scales"],
+                                           ins["rotations"], None, rsl)
+    g = torch.Generator().manual_seed(1)
+    gc, gd, ga = (torch.randn(s, generator=g).to(dev) for s in ((B, 3, H, W), (B, 1, H, W), (B, 1, H, W)))
+    torch.autograd.backward([c, d, a], [gc, gd, ga])
+    return [("batch3", "outputs", h(c), h(d), h(a), h(r)),
+            ("batch3", "grads") + tuple(h(ins[k].grad) for k in names) + (h(m2.grad),)]
+
+
+def report(label, ref, got):
     ok = got == ref
-    same = same and ok
-    print(path, "IDENTICAL" if ok else "DIFFERENT")
+    print(label, "IDENTICAL" if ok else "DIFFERENT")
     if not ok:
         for a, b in zip(ref, got):
             if a != b:
                 print("  ", a, "\n  ", b)
-sys.exit(0 if same else 1)
+    return ok
+
+
+def plain(fp):
+    return json.loads(json.dumps(fp))          # (tuples -> lists: what a saved file holds)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--save", metavar="FILE")
+    ap.add_argument("--against", metavar="FILE")
+    ap.add_argument("libs", nargs="*")
+    args = ap.parse_args()
+    ref = fingerprint()
+    for r in ref:
+        print("in-tree", r)
+    same = True
+    if args.save or args.against:
+        assert not args.libs, "library paths go with the raw-ABI mode only"
+        allfp = plain(ref + fingerprint_batch())
+        for r in allfp[len(ref):]:
+            print("in-tree", tuple(r))
+        if args.save:
+            with open(args.save, "w") as f:
+                json.dump(allfp, f, indent=1)
+        if args.against:
+            with open(args.against) as f:
+                same = report(args.against, json.load(f), allfp)
+    for path in args.libs:
+        _lib._lib = None
+        _lib.LIB_PATH = os.path.abspath(path)
+        same = report(path, ref, fingerprint()) and same
+    sys.exit(0 if same else 1)
