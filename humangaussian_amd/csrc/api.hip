@@ -53,6 +53,12 @@ struct Carver {
   size_t off = 0;
   size_t take(size_t bytes) { const size_t o = off; off = hgs_align_up(off + bytes, ALIGN); return o; }
 };
+// the device-wide scan of gridscan.h over n elements of elem bytes: its workgroups and the bytes of its block totals
+struct ScanShape { unsigned blocks; size_t bsum_bytes; };
+inline ScanShape scan_shape(size_t n, size_t elem) {
+  const size_t nb = (n + HGS_SCAN_BLOCK - 1) / HGS_SCAN_BLOCK;
+  return {(unsigned)nb, (nb + 1) * elem};
+}
 constexpr size_t HGS_LDS_BINS_MAX = 16384;   // T*4 bytes of LDS <= 64 KB
 #define HGS_BIN_WGS_PER_VIEW_MAX 512   // (256 until round 5: at 500k Gaussians a workgroup then walked 8 chunks one after the other -
                                        //  preprocess_fwd 70 -> 54 us with 512, +2 us in `tiles` (twice the histogram rows); 100k: +-0)
@@ -193,6 +199,13 @@ View make_view(const hgs_settings* s, int B, int P, int M, int64_t cap, int max_
 }
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? HGS_OK : -(1000 + (int)e); }
+
+// A header that holds a box as ordered-key images (gridscan.h): all of it zero, the box empty (bmin = all ones, bmax = 0).
+// (KnnGrid's other fields are zeroed with it; hgs_k_knn_grid_setup writes every one of them before anything reads it.)
+inline hipError_t box_init(void* hdr, size_t hdr_bytes, uint32_t* bmin, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(hdr, 0, hdr_bytes, stream);
+  return e != hipSuccess ? e : hipMemsetAsync(bmin, 0xff, 3 * sizeof(uint32_t), stream);
+}
 
 #define HGS_LAUNCH_CHECK()                       \
   do {                                           \
@@ -355,7 +368,7 @@ KnnCarve carve_knn(int32_t P) {
   c.cell_of = cv.take(n * 4);
   c.count = cv.take(((size_t)c.nc_max + 1) * 4);
   c.cursor = cv.take((size_t)c.nc_max * 4);
-  c.bsum = cv.take(((size_t)c.nc_max / 1024 + 2) * 4);
+  c.bsum = cv.take(scan_shape((size_t)c.nc_max + 1, 4).bsum_bytes);        // (sized like count[]: with the end sentinel)
   c.sorted = cv.take(n * 16);
   c.total = cv.off;
   return c;
@@ -377,17 +390,15 @@ int hgs_knn_mean_dist2_grid(int32_t P, const float* points, float* mean_dist2, v
   uint32_t* cursor = reinterpret_cast<uint32_t*>(sp + c.cursor);
   uint32_t* bsum = reinterpret_cast<uint32_t*>(sp + c.bsum);
   float4* sorted = reinterpret_cast<float4*>(sp + c.sorted);
-  // box images: min = all ones, max = zero; cell counters zero
-  hipError_t e = hipMemsetAsync(&G->bmin[0], 0xff, 12, stream);
-  if (e == hipSuccess) e = hipMemsetAsync(&G->bmax[0], 0, 12, stream);
-  if (e == hipSuccess) e = hipMemsetAsync(count, 0, ((size_t)c.nc_max + 1) * 4, stream);
+  hipError_t e = box_init(G, sizeof(KnnGrid), G->bmin, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(count, 0, ((size_t)c.nc_max + 1) * 4, stream);      // cell counters
   if (e != hipSuccess) return hip_rc(e);
-  const unsigned gp = (unsigned)((P + 255) / 256), gc = (unsigned)((c.nc_max + 1023u) / 1024u);
+  const unsigned gp = (unsigned)((P + 255) / 256), gc = scan_shape(c.nc_max, 4).blocks;
   hipLaunchKernelGGL(hgs_k_knn_bbox, dim3(gp), dim3(256), 0, stream, (int)P, points, G);
   hipLaunchKernelGGL(hgs_k_knn_grid_setup, dim3(1), dim3(64), 0, stream, (int)P, c.nc_max, G);
   hipLaunchKernelGGL(hgs_k_knn_count, dim3(gp), dim3(256), 0, stream, (int)P, points, (const KnnGrid*)G, cell_of, count);
   hipLaunchKernelGGL(hgs_k_knn_scan1, dim3(gc), dim3(1024), 0, stream, (const KnnGrid*)G, (const uint32_t*)count, bsum);
-  hipLaunchKernelGGL(hgs_k_knn_scan2, dim3(1), dim3(1024), 0, stream, G, bsum);
+  hipLaunchKernelGGL(hgs_k_knn_scan2, dim3(1), dim3(1024), 0, stream, (const KnnGrid*)G, bsum);
   hipLaunchKernelGGL(hgs_k_knn_scan3, dim3(gc), dim3(1024), 0, stream, (int)P, G, count, cursor, (const uint32_t*)bsum);
   hipLaunchKernelGGL(hgs_k_knn_scatter, dim3(gp), dim3(256), 0, stream, (int)P, points, (const uint32_t*)cell_of, cursor, sorted);
   hipLaunchKernelGGL(hgs_k_knn_search, dim3(gp), dim3(256), 0, stream, (int)P, (const KnnGrid*)G, (const uint32_t*)count,
@@ -868,7 +879,7 @@ int hgs_densify_masks(int32_t P, const float* xyz_gradient_accum, const float* d
 }
 
 size_t hgs_compact_scratch_bytes(int32_t P) {
-  return hgs_align_up(((size_t)(P > 0 ? P : 0) + 1023) / 1024 * 4 + 4, ALIGN);
+  return hgs_align_up(scan_shape((size_t)(P > 0 ? P : 0), 4).bsum_bytes, ALIGN);
 }
 
 int hgs_compact_index(int32_t P, const uint8_t* keep, int32_t* src_of_dst, uint32_t* num_kept, void* scratch,
@@ -880,7 +891,7 @@ int hgs_compact_index(int32_t P, const uint8_t* keep, int32_t* src_of_dst, uint3
     return e == hipSuccess ? HGS_OK : hip_rc(e);
   }
   if (!keep || !src_of_dst || !scratch) return HGS_EINVAL;
-  const int nb = (P + 1023) / 1024;
+  const int nb = (int)scan_shape((size_t)P, 4).blocks;
   uint32_t* blocks = static_cast<uint32_t*>(scratch);
   hipLaunchKernelGGL(hgs_k_keep_count, dim3(nb), dim3(1024), 0, stream, (int)P, keep, blocks);
   hipLaunchKernelGGL(hgs_k_keep_scan, dim3(1), dim3(1024), 0, stream, nb, blocks, num_kept);
@@ -923,7 +934,7 @@ MeshCarve carve_mesh(int32_t F, uint32_t ncells, uint64_t nrefs) {
   c.tris = cv.take((size_t)F * 48);
   c.start = cv.take(((size_t)ncells + 1) * 4);
   c.cursor = cv.take((size_t)ncells * 4);
-  c.bsum = cv.take(((size_t)ncells / 1024 + 2) * 4);
+  c.bsum = cv.take(scan_shape((size_t)ncells + 1, 4).bsum_bytes);          // (sized like start[]: with the end sentinel)
   c.refs = cv.take((size_t)nrefs * 4);
   c.total = cv.off;
   return c;
@@ -943,8 +954,7 @@ int hgs_mesh_grid_plan(int32_t V, const float* vertices, int32_t F, const int32_
                        void* stream_) {
   if (V < 0 || F < 1 || !info || !faces || (V > 0 && !vertices)) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  hipError_t e = hipMemsetAsync(info, 0, sizeof(hgs_mesh_grid_info), stream);
-  if (e == hipSuccess) e = hipMemsetAsync(&info->bmin[0], 0xff, 12, stream);
+  const hipError_t e = box_init(info, sizeof(hgs_mesh_grid_info), info->bmin, stream);
   if (e != hipSuccess) return hip_rc(e);
   if (V > 0) hipLaunchKernelGGL(hgs_k_mesh_bbox, dim3((V + 255) / 256), dim3(256), 0, stream, (int)V, vertices, info);
   hipLaunchKernelGGL(hgs_k_mesh_grid_setup, dim3(1), dim3(64), 0, stream, (int)F, info);
@@ -978,7 +988,7 @@ int hgs_mesh_grid_build(int32_t V, const float* vertices, int32_t F, const int32
   G.nrefs = (uint32_t)in.num_refs;
   G.off_tris = c.tris; G.off_start = c.start; G.off_cursor = c.cursor; G.off_bsum = c.bsum; G.off_refs = c.refs;
   const unsigned long long n_init = std::max<unsigned long long>((unsigned long long)in.ncells + 1, (unsigned long long)F);
-  const unsigned gf = (unsigned)((F + 255) / 256), gc = (in.ncells + 1023u) / 1024u;
+  const unsigned gf = (unsigned)((F + 255) / 256), gc = scan_shape(in.ncells, 4).blocks;
   hipLaunchKernelGGL(hgs_k_mesh_grid_init, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, stream, G, (int)V,
                      vertices, faces, grid);
   hipLaunchKernelGGL(hgs_k_mesh_bin, dim3(gf), dim3(256), 0, stream, G, grid, 0);
@@ -1058,7 +1068,7 @@ McCarve carve_mc(size_t N) {
   McCarve c;
   Carver cv;
   c.offs = cv.take((N + 1) * 8);
-  c.bsum = cv.take(((N + 1023) / 1024 + 1) * 8);
+  c.bsum = cv.take(scan_shape(N, 8).bsum_bytes);
   c.mask = cv.take(N);
   c.total = cv.off;
   return c;
@@ -1088,8 +1098,7 @@ int hgs_field_plan(int32_t P, const float* xyz, const float* opacity, const floa
   const FieldPlanPtrs pp = field_plan_ptrs(c, plan);
   const FieldDims D = {P, resolution, num_blocks, resolution / num_blocks};
   const uint32_t nblocks = (uint32_t)(num_blocks * num_blocks * num_blocks);
-  hipError_t e = hipMemsetAsync(info, 0, sizeof(hgs_field_info), stream);
-  if (e == hipSuccess) e = hipMemsetAsync(&info->bmin[0], 0xff, 12, stream);
+  hipError_t e = box_init(info, sizeof(hgs_field_info), info->bmin, stream);
   if (e == hipSuccess) e = hipMemsetAsync(pp.counts, 0, (size_t)nblocks * 4, stream);
   if (e != hipSuccess) return hip_rc(e);
   const unsigned gp = (unsigned)((P + 255) / 256);
@@ -1146,7 +1155,7 @@ int hgs_mc_count(const float* field, int32_t X, int32_t Y, int32_t Z, float thre
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const McDims D = {X, Y, Z, (uint32_t)((size_t)X * Y * Z)};
   const McPtrs p = mc_ptrs(carve_mc(D.N), scratch);
-  const unsigned g1k = (D.N + 1023u) / 1024u;
+  const unsigned g1k = scan_shape(D.N, 8).blocks;
   hipLaunchKernelGGL(hgs_k_mc_count, dim3((D.N + 255u) / 256u), dim3(256), 0, stream, D, field, threshold, p);
   hipLaunchKernelGGL(hgs_k_mc_scan1, dim3(g1k), dim3(1024), 0, stream, D, p);
   hipLaunchKernelGGL(hgs_k_mc_scan2, dim3(1), dim3(1024), 0, stream, D, p, info);

@@ -105,22 +105,8 @@ hgs_k_keep_count(int P, const uint8_t* __restrict__ keep, uint32_t* __restrict__
 
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_keep_scan(int nblocks, uint32_t* __restrict__ block_count, uint32_t* __restrict__ total) {
-  __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int k = base + threadIdx.x;
-    const uint32_t v = k < nblocks ? block_count[k] : 0u;
-    uint32_t tot;
-    const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot);
-    const uint32_t c = carry;
-    if (k < nblocks) block_count[k] = c + ex;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = c + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
+  const uint32_t kept = hgs_scan_carry((uint32_t)nblocks, block_count, block_count);      // gridscan.h
+  if (threadIdx.x == 0) *total = kept;
 }
 
 // dst row of kept source row i = block base + rank of i among the kept rows of its block

@@ -1,6 +1,6 @@
 // fields.hip - the density field of the Gaussians on a regular grid and its iso-surface (include/hgs_rast.h: hgs_field_*,
-// hgs_mc_*; the reference's GaussianModel.extract_fields + mcubes.marching_cubes).  Included by api.hip after knn.hip
-// (knn_key / knn_unkey) - one translation unit, under the no-scratch rule of tests/test_kernel_resources_cpu.py.
+// hgs_mc_*; the reference's GaussianModel.extract_fields + mcubes.marching_cubes).  Included by api.hip - one translation
+// unit, under the no-scratch rule of tests/test_kernel_resources_cpu.py.  Box reduction and scans: gridscan.h.
 //
 // Field:  bbox -> setup -> gauss (record + reached block range per Gaussian) -> lists(count)      [hgs_field_plan]
 //         order (scan of the counts, blocks heaviest first) -> lists(fill) -> eval                  [hgs_field_eval]
@@ -47,21 +47,11 @@ __device__ __forceinline__ bool field_kept(int i, const float* __restrict__ xyz,
 extern "C" __global__ void __launch_bounds__(256)
 hgs_k_field_bbox(int P, const float* __restrict__ xyz, const float* __restrict__ opacity, hgs_field_info* __restrict__ info) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  float3 p;
+  float3 p = make_float3(0.f, 0.f, 0.f);
   const bool kept = i < P && field_kept(i, xyz, opacity, p);
-  if (kept) { lo[0] = hi[0] = knn_key(p.x); lo[1] = hi[1] = knn_key(p.y); lo[2] = hi[2] = knn_key(p.z); }
+  hgs_box_reduce(kept, p.x, p.y, p.z, info->bmin, info->bmax);
   const uint32_t n = (uint32_t)__popcll(__ballot(kept));
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    hi[a] = hgs_wave_max_u32(hi[a]);
-    lo[a] = ~hgs_wave_max_u32(~lo[a]);
-  }
-  if ((threadIdx.x & 63) == 0 && n) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { atomicMin(&info->bmin[a], lo[a]); atomicMax(&info->bmax[a], hi[a]); }
-    atomicAdd(&info->num_kept, n);
-  }
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&info->num_kept, n);
 }
 
 // one workgroup: centre, extent and scale from the box; the blocks' bounds from the axis
@@ -75,7 +65,7 @@ hgs_k_field_setup(FieldDims D, const float* __restrict__ axis, float grow, Field
   if (t != 0) return;
   float ext = 0.0f;
   for (int a = 0; a < 3; ++a) {
-    const float mn = info->num_kept ? knn_unkey(info->bmin[a]) : 0.0f, mx = info->num_kept ? knn_unkey(info->bmax[a]) : 0.0f;
+    const float mn = info->num_kept ? hgs_key_float(info->bmin[a]) : 0.0f, mx = info->num_kept ? hgs_key_float(info->bmax[a]) : 0.0f;
     info->center[a] = (mn + mx) / 2.0f;
     ext = fmaxf(ext, mx - mn);
   }
@@ -182,26 +172,14 @@ hgs_k_field_lists(FieldDims D, FieldPlanPtrs pp, FieldListPtrs lp, int fill, hgs
 // first (the evaluation's workgroups start in this order; where a block stands inside its class changes no result)
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_field_order(FieldDims D, FieldPlanPtrs pp, FieldListPtrs lp) {
-  __shared__ uint32_t wtot[16];
   __shared__ uint32_t cls_n[33], cls_at[33];
   const uint32_t nblocks = (uint32_t)(D.nb * D.nb * D.nb);
   if (threadIdx.x < 33) cls_n[threadIdx.x] = 0u;
   __syncthreads();
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nblocks; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t v = b < nblocks ? pp.counts[b] : 0u;
-    uint32_t tot;
-    const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot);
-    if (b < nblocks) {
-      lp.start[b] = carry + ex;
-      atomicAdd(&cls_n[32 - __clz(v)], 1u);
-    }
-    carry += tot;
-    __syncthreads();
-  }
+  for (uint32_t b = threadIdx.x; b < nblocks; b += 1024u) atomicAdd(&cls_n[32 - __clz(pp.counts[b])], 1u);
+  const uint32_t total = hgs_scan_carry(nblocks, pp.counts, lp.start);      // (its barriers also order the histogram)
   if (threadIdx.x == 0) {
-    lp.start[nblocks] = carry;
+    lp.start[nblocks] = total;
     uint32_t at = 0;
     for (int c = 32; c >= 0; --c) { cls_at[c] = at; at += cls_n[c]; }
   }
@@ -302,47 +280,23 @@ hgs_k_mc_count(McDims D, const float* __restrict__ f, float thr, McPtrs p) {
   p.offs[i] = make_uint2((uint32_t)__popc(m), nt);
 }
 
-// exclusive scan of offs[0 .. N) in place, both components; offs[N] and `info` receive the totals
+// exclusive scan of offs[0 .. N) in place, both components (gridscan.h on uint2); offs[N] and `info` receive the totals
 extern "C" __global__ void __launch_bounds__(1024)
-hgs_k_mc_scan1(McDims D, McPtrs p) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const uint2 v = i < D.N ? p.offs[i] : make_uint2(0u, 0u);
-  uint32_t tx, ty;
-  hgs_block_excl_scan<1024>(v.x, wtot, tx);
-  hgs_block_excl_scan<1024>(v.y, wtot, ty);
-  if (threadIdx.x == 0) p.bsum[blockIdx.x] = make_uint2(tx, ty);
-}
+hgs_k_mc_scan1(McDims D, McPtrs p) { hgs_scan_totals(D.N, p.offs, p.bsum); }
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_mc_scan2(McDims D, McPtrs p, hgs_mc_info* __restrict__ info) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t nb = (D.N + 1023u) / 1024u;
-  uint2 carry = make_uint2(0u, 0u);
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint2 v = b < nb ? p.bsum[b] : make_uint2(0u, 0u);
-    uint32_t tx, ty;
-    const uint32_t ex = hgs_block_excl_scan<1024>(v.x, wtot, tx);
-    const uint32_t ey = hgs_block_excl_scan<1024>(v.y, wtot, ty);
-    if (b < nb) p.bsum[b] = make_uint2(carry.x + ex, carry.y + ey);
-    carry.x += tx; carry.y += ty;
-    __syncthreads();
-  }
+  const uint2 total = hgs_scan_carry((D.N + HGS_SCAN_BLOCK - 1u) / HGS_SCAN_BLOCK, p.bsum, p.bsum);
   if (threadIdx.x == 0) {
-    p.offs[D.N] = carry;
-    info->num_vertices = carry.x;
-    info->num_triangles = carry.y;
+    p.offs[D.N] = total;
+    info->num_vertices = total.x;
+    info->num_triangles = total.y;
   }
 }
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_mc_scan3(McDims D, McPtrs p) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const uint2 v = i < D.N ? p.offs[i] : make_uint2(0u, 0u), base = p.bsum[blockIdx.x];
-  uint32_t tx, ty;
-  const uint32_t ex = hgs_block_excl_scan<1024>(v.x, wtot, tx);
-  const uint32_t ey = hgs_block_excl_scan<1024>(v.y, wtot, ty);
-  if (i < D.N) p.offs[i] = make_uint2(base.x + ex, base.y + ey);
+  uint32_t i;
+  uint2 ex, v;
+  if (hgs_scan_prefix(D.N, p.offs, p.bsum, i, ex, v)) p.offs[i] = ex;
 }
 
 extern "C" __global__ void __launch_bounds__(256)

@@ -270,6 +270,8 @@ __device__ __forceinline__ uint32_t hgs_block_excl_scan(uint32_t v, uint32_t* wt
   return base + incl - v;
 }
 
+#include "gridscan.h"   // on top of the two primitives above: ordered float keys, box reduction, device-wide scan, grid fit
+
 // ---- device timeline (debug builds only: -DHGS_TIMELINE, tools/timeline.py) --------------------------
 // Every wave of an instrumented kernel leaves (start, end, hardware id, tag) in a static device
 // table (defined in api.hip: the kernels of that translation unit); wall_clock64 ticks at 100 MHz.

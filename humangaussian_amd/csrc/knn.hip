@@ -26,7 +26,7 @@
 
 // scratch layout (hgs_knn_scratch_bytes): header | cell_of[P] | count[NC + 1] -> start | cursor[NC] | block sums | sorted[P] float4
 struct KnnGrid {
-  uint32_t bmin[3], bmax[3];           // ordered-integer images of the box (knn_key)
+  uint32_t bmin[3], bmax[3];           // ordered-integer images of the box (hgs_float_key)
   uint32_t gx, gy, gz, ncells;         // grid
   float ox, oy, oz, inv_h, h;          // origin, 1 / cell edge, cell edge
   uint32_t max_count;                  // fullest cell
@@ -34,62 +34,27 @@ struct KnnGrid {
   uint32_t pad;
 };
 
-// float <-> unsigned key with the same order (atomicMin / atomicMax on floats of any sign)
-__device__ __forceinline__ uint32_t knn_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float knn_unkey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 extern "C" __global__ void __launch_bounds__(256)
 hgs_k_knn_bbox(int P, const float* __restrict__ pts, KnnGrid* __restrict__ G) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  if (i < P) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = knn_key(pts[3 * (size_t)i + a]);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    hi[a] = hgs_wave_max_u32(hi[a]);
-    lo[a] = ~hgs_wave_max_u32(~lo[a]);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { atomicMin(&G->bmin[a], lo[a]); atomicMax(&G->bmax[a], hi[a]); }
-  }
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  if (i < P) { x = pts[3 * (size_t)i]; y = pts[3 * (size_t)i + 1]; z = pts[3 * (size_t)i + 2]; }
+  hgs_box_reduce(i < P, x, y, z, G->bmin, G->bmax);
 }
 
-// one thread: the grid from the box.  nc_max = cells the scratch was sized for.
+// one thread: the grid from the box (gridscan.h), first cell edge cbrt(2 V / P).  nc_max = cells the scratch was sized for.
 extern "C" __global__ void hgs_k_knn_grid_setup(int P, uint32_t nc_max, KnnGrid* __restrict__ G) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   float lo[3], ext[3];
   for (int a = 0; a < 3; ++a) {
-    lo[a] = knn_unkey(G->bmin[a]);
-    ext[a] = knn_unkey(G->bmax[a]) - lo[a];
+    lo[a] = hgs_key_float(G->bmin[a]);
+    ext[a] = hgs_key_float(G->bmax[a]) - lo[a];
     if (!(ext[a] >= 0.0f) || !(ext[a] < 3.0e38f)) ext[a] = 0.0f;      // NaN / inf coordinates: that axis collapses
   }
   const float emax = fmaxf(ext[0], fmaxf(ext[1], ext[2]));
-  // flat axes (a planar or collinear cloud) get the thickness of one cell instead of 0
   float h = 1.0f;
   uint32_t g[3] = {1u, 1u, 1u};
-  if (emax > 0.0f && P > 8) {
-    const float floor_ext = emax * 1e-3f;
-    const float vol = fmaxf(ext[0], floor_ext) * fmaxf(ext[1], floor_ext) * fmaxf(ext[2], floor_ext);
-    h = cbrtf(2.0f * vol / (float)P);
-    for (int it = 0; it < 64; ++it) {                    // grow the cells until the grid fits the scratch
-      unsigned long long n = 1;
-      for (int a = 0; a < 3; ++a) {
-        const float c = floorf(ext[a] / h) + 1.0f;
-        g[a] = c < 1.0f ? 1u : (c > 4096.0f ? 4096u : (uint32_t)c);
-        n *= g[a];
-      }
-      if (n <= nc_max && ext[0] / h < 4095.0f && ext[1] / h < 4095.0f && ext[2] / h < 4095.0f) break;
-      h *= 1.26f;
-    }
-  }
+  if (emax > 0.0f && P > 8) h = hgs_grid_fit(ext, cbrtf(2.0f * hgs_grid_volume(ext, emax) / (float)P), nc_max, g);
   G->gx = g[0]; G->gy = g[1]; G->gz = g[2];
   G->ncells = g[0] * g[1] * g[2];
   if (G->ncells > nc_max) { G->gx = G->gy = G->gz = 1u; G->ncells = 1u; }      // (cannot happen; stays in bounds if it does)
@@ -99,10 +64,10 @@ extern "C" __global__ void hgs_k_knn_grid_setup(int P, uint32_t nc_max, KnnGrid*
 }
 
 __device__ __forceinline__ void knn_cell_of(const KnnGrid& G, float x, float y, float z, int& cx, int& cy, int& cz) {
-  // (non-finite coordinates land in cell 0 of their axis: fmaxf / fminf drop NaN)
-  cx = (int)fminf(fmaxf(floorf((x - G.ox) * G.inv_h), 0.0f), (float)(G.gx - 1u));
-  cy = (int)fminf(fmaxf(floorf((y - G.oy) * G.inv_h), 0.0f), (float)(G.gy - 1u));
-  cz = (int)fminf(fmaxf(floorf((z - G.oz) * G.inv_h), 0.0f), (float)(G.gz - 1u));
+  // (non-finite coordinates land in cell 0 of their axis)
+  cx = hgs_grid_cell1(x, G.ox, G.inv_h, (int)G.gx);
+  cy = hgs_grid_cell1(y, G.oy, G.inv_h, (int)G.gy);
+  cz = hgs_grid_cell1(z, G.oz, G.inv_h, (int)G.gz);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -118,41 +83,25 @@ hgs_k_knn_count(int P, const float* __restrict__ pts, const KnnGrid* __restrict_
   atomicAdd(&count[c], 1u);
 }
 
-// exclusive scan of count[0 .. ncells) in place (count[ncells] = P), three passes of 1024-cell blocks
+// exclusive scan of count[0 .. ncells) in place (count[ncells] = P): the three passes of gridscan.h.  ncells is decided on
+// the device: the grids are sized for nc_max cells, the workgroups behind the last block return at once.
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_knn_scan1(const KnnGrid* __restrict__ Gp, const uint32_t* __restrict__ count, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t n = Gp->ncells, i = blockIdx.x * 1024u + threadIdx.x;
-  if (blockIdx.x * 1024u >= n) return;
-  uint32_t tot;
-  hgs_block_excl_scan<1024>(i < n ? count[i] : 0u, wtot, tot);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+  const uint32_t n = Gp->ncells;
+  if (blockIdx.x * HGS_SCAN_BLOCK >= n) return;
+  hgs_scan_totals(n, count, bsum);
 }
 extern "C" __global__ void __launch_bounds__(1024)
-hgs_k_knn_scan2(KnnGrid* __restrict__ Gp, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t nb = (Gp->ncells + 1023u) / 1024u;
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t v = b < nb ? bsum[b] : 0u;
-    uint32_t tot;
-    const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot);
-    if (b < nb) bsum[b] = carry + ex;
-    carry += tot;
-    __syncthreads();
-  }
+hgs_k_knn_scan2(const KnnGrid* __restrict__ Gp, uint32_t* __restrict__ bsum) {
+  hgs_scan_carry((Gp->ncells + HGS_SCAN_BLOCK - 1u) / HGS_SCAN_BLOCK, bsum, bsum);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_knn_scan3(int P, KnnGrid* __restrict__ Gp, uint32_t* __restrict__ count, uint32_t* __restrict__ cursor,
                 const uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t wtot[16];
-  const uint32_t n = Gp->ncells, i = blockIdx.x * 1024u + threadIdx.x;
-  if (blockIdx.x * 1024u >= n) return;
-  const uint32_t v = i < n ? count[i] : 0u;
-  uint32_t tot;
-  const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot) + bsum[blockIdx.x];
-  if (i < n) { count[i] = ex; cursor[i] = ex; }
+  const uint32_t n = Gp->ncells;
+  if (blockIdx.x * HGS_SCAN_BLOCK >= n) return;
+  uint32_t i, ex, v;
+  if (hgs_scan_prefix(n, count, bsum, i, ex, v)) { count[i] = ex; cursor[i] = ex; }
   if (i == n - 1u) count[n] = (uint32_t)P;
   const uint32_t mx = hgs_wave_max_u32(v);
   if ((threadIdx.x & 63) == 0 && mx) {

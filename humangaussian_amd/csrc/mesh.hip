@@ -9,7 +9,8 @@
 //   raystab: the point is inside iff all 64 rays +-d_i (32 fixed Fibonacci-lattice directions) hit a face at t > 0
 //   (watertight ray / triangle test), and then dist is negated.
 //
-// Acceleration, MI355X-first and without a host round trip inside a query (the knn.hip pattern):
+// Acceleration, MI355X-first and without a host round trip inside a query (the knn.hip pattern; box, grid fit and scan are
+// gridscan.h's):
 //   plan   bounding box of the finite vertices (wave max, one ordered-integer atomic per wave and axis), a uniform grid
 //          sized on the device from it (cell edge cbrt(vol / 8F): ~1-4 faces per occupied cell of a body mesh), and the
 //          number of (face, cell) references when every face is binned into the cells of its bounding box;
@@ -169,33 +170,19 @@ __device__ __forceinline__ void mesh_write(int i, const MeshBest& B, bool inside
 extern "C" __global__ void __launch_bounds__(256)
 hgs_k_mesh_bbox(int V, const float* __restrict__ vtx, hgs_mesh_grid_info* __restrict__ info) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  if (i < V) {
-    const float3 p = make_float3(vtx[3 * (size_t)i], vtx[3 * (size_t)i + 1], vtx[3 * (size_t)i + 2]);
-    if (m3finite(p)) {                                 // non-finite vertices do not stretch the box
-      lo[0] = hi[0] = knn_key(p.x); lo[1] = hi[1] = knn_key(p.y); lo[2] = hi[2] = knn_key(p.z);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    hi[a] = hgs_wave_max_u32(hi[a]);
-    lo[a] = ~hgs_wave_max_u32(~lo[a]);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { atomicMin(&info->bmin[a], lo[a]); atomicMax(&info->bmax[a], hi[a]); }
-  }
+  float3 p = make_float3(0.f, 0.f, 0.f);
+  if (i < V) p = make_float3(vtx[3 * (size_t)i], vtx[3 * (size_t)i + 1], vtx[3 * (size_t)i + 2]);
+  hgs_box_reduce(i < V && m3finite(p), p.x, p.y, p.z, info->bmin, info->bmax);     // non-finite vertices do not stretch the box
 }
 
-// one thread: the grid from the box.  Cell edge cbrt(vol / 8F), flat axes thickened to 1e-3 of the longest, grown by
-// 1.26 until the grid has at most min(16 F, 4 M) cells and at most 4096 per axis (the knn.hip rule).
+// one thread: the grid from the box (gridscan.h), first cell edge cbrt(vol / 8F), at most min(16 F, 4 M) cells
 extern "C" __global__ void hgs_k_mesh_grid_setup(int F, hgs_mesh_grid_info* __restrict__ info) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const bool empty = info->bmin[0] > info->bmax[0];     // no finite vertex
   float lo[3], ext[3];
   for (int a = 0; a < 3; ++a) {
-    lo[a] = empty ? 0.0f : knn_unkey(info->bmin[a]);
-    ext[a] = empty ? 0.0f : knn_unkey(info->bmax[a]) - lo[a];
+    lo[a] = empty ? 0.0f : hgs_key_float(info->bmin[a]);
+    ext[a] = empty ? 0.0f : hgs_key_float(info->bmax[a]) - lo[a];
     if (!(ext[a] >= 0.0f) || !(ext[a] < 3.0e38f)) ext[a] = 0.0f;
   }
   const uint32_t nc_max = (uint32_t)min(max(16ll * F, 64ll), (long long)HGS_MESH_MAX_CELLS);
@@ -203,19 +190,7 @@ extern "C" __global__ void hgs_k_mesh_grid_setup(int F, hgs_mesh_grid_info* __re
   float h = 1.0f;
   uint32_t g[3] = {1u, 1u, 1u};
   if (emax > 0.0f) {
-    const float floor_ext = emax * 1e-3f;
-    const float vol = fmaxf(ext[0], floor_ext) * fmaxf(ext[1], floor_ext) * fmaxf(ext[2], floor_ext);
-    h = cbrtf(vol / (8.0f * (float)F));
-    for (int it = 0; it < 64; ++it) {
-      unsigned long long n = 1;
-      for (int a = 0; a < 3; ++a) {
-        const float c = floorf(ext[a] / h) + 1.0f;
-        g[a] = c < 1.0f ? 1u : (c > 4096.0f ? 4096u : (uint32_t)c);
-        n *= g[a];
-      }
-      if (n <= nc_max && ext[0] / h < 4095.0f && ext[1] / h < 4095.0f && ext[2] / h < 4095.0f) break;
-      h *= 1.26f;
-    }
+    h = hgs_grid_fit(ext, cbrtf(hgs_grid_volume(ext, emax) / (8.0f * (float)F)), nc_max, g);
     if ((unsigned long long)g[0] * g[1] * g[2] > nc_max) { g[0] = g[1] = g[2] = 1u; h = emax; }   // (cannot happen)
   }
   for (int a = 0; a < 3; ++a) { info->dims[a] = (int32_t)g[a]; info->origin[a] = lo[a]; }
@@ -227,20 +202,16 @@ extern "C" __global__ void hgs_k_mesh_grid_setup(int F, hgs_mesh_grid_info* __re
 
 struct MeshCells { int x0, y0, z0, x1, y1, z1; };
 
-__device__ __forceinline__ int mesh_cell1(float x, float o, float inv_h, int g) {
-  return (int)fminf(fmaxf(floorf((x - o) * inv_h), 0.0f), (float)(g - 1));       // (NaN -> 0: fmaxf drops it)
-}
-
 // cells of the face's bounding box (the same fp32 operations at plan, build and query time)
 __device__ __forceinline__ MeshCells mesh_face_cells(float3 a, float3 b, float3 c, const float o[3], float inv_h,
                                                      const int g[3]) {
   MeshCells r;
-  r.x0 = mesh_cell1(fminf(a.x, fminf(b.x, c.x)), o[0], inv_h, g[0]);
-  r.x1 = mesh_cell1(fmaxf(a.x, fmaxf(b.x, c.x)), o[0], inv_h, g[0]);
-  r.y0 = mesh_cell1(fminf(a.y, fminf(b.y, c.y)), o[1], inv_h, g[1]);
-  r.y1 = mesh_cell1(fmaxf(a.y, fmaxf(b.y, c.y)), o[1], inv_h, g[1]);
-  r.z0 = mesh_cell1(fminf(a.z, fminf(b.z, c.z)), o[2], inv_h, g[2]);
-  r.z1 = mesh_cell1(fmaxf(a.z, fmaxf(b.z, c.z)), o[2], inv_h, g[2]);
+  r.x0 = hgs_grid_cell1(fminf(a.x, fminf(b.x, c.x)), o[0], inv_h, g[0]);
+  r.x1 = hgs_grid_cell1(fmaxf(a.x, fmaxf(b.x, c.x)), o[0], inv_h, g[0]);
+  r.y0 = hgs_grid_cell1(fminf(a.y, fminf(b.y, c.y)), o[1], inv_h, g[1]);
+  r.y1 = hgs_grid_cell1(fmaxf(a.y, fmaxf(b.y, c.y)), o[1], inv_h, g[1]);
+  r.z0 = hgs_grid_cell1(fminf(a.z, fminf(b.z, c.z)), o[2], inv_h, g[2]);
+  r.z1 = hgs_grid_cell1(fmaxf(a.z, fmaxf(b.z, c.z)), o[2], inv_h, g[2]);
   return r;
 }
 
@@ -324,41 +295,23 @@ hgs_k_mesh_bin(MeshGridHdr G, void* grid, int pass) {
       }
 }
 
-// exclusive scan of start[0 .. ncells) in place (start[ncells] = total), three passes of 1024-cell blocks
+// exclusive scan of start[0 .. ncells) in place (start[ncells] = total): the three passes of gridscan.h
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_mesh_scan1(MeshGridHdr G, void* grid) {
-  __shared__ uint32_t wtot[16];
   const MeshGridPtrs p = mesh_ptrs(G, grid);
-  const uint32_t n = G.ncells, i = blockIdx.x * 1024u + threadIdx.x;
-  uint32_t tot;
-  hgs_block_excl_scan<1024>(i < n ? p.start[i] : 0u, wtot, tot);
-  if (threadIdx.x == 0) p.bsum[blockIdx.x] = tot;
+  hgs_scan_totals(G.ncells, p.start, p.bsum);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_mesh_scan2(MeshGridHdr G, void* grid) {
-  __shared__ uint32_t wtot[16];
   const MeshGridPtrs p = mesh_ptrs(G, grid);
-  const uint32_t nb = (G.ncells + 1023u) / 1024u;
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t v = b < nb ? p.bsum[b] : 0u;
-    uint32_t tot;
-    const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot);
-    if (b < nb) p.bsum[b] = carry + ex;
-    carry += tot;
-    __syncthreads();
-  }
+  hgs_scan_carry((G.ncells + HGS_SCAN_BLOCK - 1u) / HGS_SCAN_BLOCK, p.bsum, p.bsum);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 hgs_k_mesh_scan3(MeshGridHdr G, void* grid) {
-  __shared__ uint32_t wtot[16];
   const MeshGridPtrs p = mesh_ptrs(G, grid);
-  const uint32_t n = G.ncells, i = blockIdx.x * 1024u + threadIdx.x;
-  const uint32_t v = i < n ? p.start[i] : 0u;
-  uint32_t tot;
-  const uint32_t ex = hgs_block_excl_scan<1024>(v, wtot, tot) + p.bsum[blockIdx.x];
-  if (i < n) { p.start[i] = ex; p.cursor[i] = ex; }
+  const uint32_t n = G.ncells;
+  uint32_t i, ex, v;
+  if (hgs_scan_prefix(n, p.start, p.bsum, i, ex, v)) { p.start[i] = ex; p.cursor[i] = ex; }
   if (i == n - 1u) p.start[n] = ex + v;
 }
 
@@ -386,8 +339,8 @@ __device__ __forceinline__ bool mesh_cell_faces(const MeshGridHdr& G, const Mesh
 __device__ __forceinline__ MeshBest mesh_grid_closest(const MeshGridHdr& G, const MeshGridPtrs& p, float3 q) {
   MeshBest B = {__int_as_float(0x7f800000), 0.0f, 0.0f, 0x7fffffff};
   const int gx = G.gx, gy = G.gy, gz = G.gz;
-  const int cx = mesh_cell1(q.x, G.ox, G.inv_h, gx), cy = mesh_cell1(q.y, G.oy, G.inv_h, gy),
-            cz = mesh_cell1(q.z, G.oz, G.inv_h, gz);
+  const int cx = hgs_grid_cell1(q.x, G.ox, G.inv_h, gx), cy = hgs_grid_cell1(q.y, G.oy, G.inv_h, gy),
+            cz = hgs_grid_cell1(q.z, G.oz, G.inv_h, gz);
   const float rx = q.x - G.ox, ry = q.y - G.oy, rz = q.z - G.oz;
   const float margin = 1e-3f * G.h + 1e-5f * fmaxf(G.cmax, fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z))));
   auto consider = [&](float3 a, float3 b, float3 c, int f) { mesh_consider(B, q, a, b, c, f); return false; };

@@ -106,6 +106,25 @@ def test_prune_rows_equals_boolean_indexing_for_all_tensors():
     assert torch.equal(allk[0].cpu(), tensors[3])
 
 
+def test_prune_rows_past_one_round_of_the_block_scan():
+    """More than 1024 blocks of 1024 rows: the one-workgroup pass of the scan (gridscan.h: hgs_scan_carry) runs a second
+    round and the blocks behind 2^20 rows take their base from the carry.  1026 blocks, one row in the last."""
+    P = (1 << 20) + 1024 + 1
+    g = torch.Generator().manual_seed(5)
+    keep = torch.rand(P, generator=g) < 0.6
+    keep[(1 << 20) - 1] = keep[1 << 20] = keep[P - 1] = True
+    keep = keep.to(DEV)
+    tensors = [torch.randn(P, 3, generator=g).to(DEV), torch.randn(P, generator=g).to(DEV)]
+    out = densify.prune_rows(keep, tensors)
+    for got, t in zip(out, tensors):
+        assert got.shape == t[keep].shape and torch.equal(got, t[keep])
+    assert torch.equal(out[1][-1], tensors[1][P - 1])
+    allk = densify.prune_rows(torch.ones(P, dtype=torch.bool, device=DEV), tensors)
+    assert torch.equal(allk[0], tensors[0]) and torch.equal(allk[1], tensors[1])
+    none = densify.prune_rows(torch.zeros(P, dtype=torch.bool, device=DEV), tensors)
+    assert none[0].shape == (0, 3) and none[1].shape == (0,)
+
+
 def test_reanchor_matches_the_reference_numpy_pass():
     """animation.py:384-403 in numpy (as the reference runs it) vs the device pass."""
     rng = np.random.default_rng(3)

@@ -176,6 +176,57 @@ def test_marching_cubes_sphere_torus_and_non_cubic_fields():
     assert v[:, 0].max() <= 22 and v[:, 1].max() <= 30 and v[:, 2].max() <= 16 and v.min() >= 0
 
 
+def _two_spheres(shape, boxes, centres, r=6.4):
+    """-r everywhere, inside each box (lo, hi) the signed distance field of a sphere of radius r: the boxes' faces lie outside"""
+    field = np.full(shape, -r, np.float32)
+    for (lo, hi), c in zip(boxes, centres):
+        g = np.stack(np.meshgrid(*[np.arange(a, b, dtype=np.float64) for a, b in zip(lo, hi)], indexing="ij"), -1)
+        field[tuple(slice(a, b) for a, b in zip(lo, hi))] = (r - np.linalg.norm(g - np.array(c), axis=-1)).astype(np.float32)
+    return field
+
+
+# (field shape, the two crops, the spheres' centres).  The first field has 1,056,768 samples, i.e. 1032 scan blocks, and
+# its second sphere near index (53, 117, 118) - flat index ~890k, still inside the first round of 1024 blocks: there the
+# blocks behind 2^20 and the totals take the carry, no vertex does.  In the second field the second
+# sphere lies entirely behind flat index 2^20 (x >= 4096 with 256 samples per x): every vertex and triangle offset of it
+# is the first sphere's total, carried into the second round, plus a prefix inside that round.
+TWO_SPHERES = {
+    "64x128x129": ((64, 128, 129), [((0, 0, 0), (24, 24, 24)), ((42, 106, 107), (64, 128, 129))],
+                   [(10.13, 9.79, 10.07), (53.13, 116.79, 118.07)]),
+    "4120x16x16": ((4120, 16, 16), [((0, 0, 0), (24, 16, 16)), ((4097, 0, 0), (4120, 16, 16))],
+                   [(10.13, 7.62, 7.41), (4105.13, 7.62, 7.41)]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(TWO_SPHERES))
+def test_marching_cubes_offsets_carry_past_one_round_of_the_block_scan(case):
+    """More than 2^20 samples: the one-workgroup pass of the (vertices, triangles) scan (gridscan.h: hgs_scan_carry on
+    uint2) runs a second round.  Two spheres; the surface of the whole field must be the surfaces of the two cropped
+    sub-boxes (each at most 32^3: the single-round path test_marching_cubes_sphere_torus_and_non_cubic_fields checks), one
+    behind the other: triangles are emitted in flat-index order and cropping preserves that order, so the triangle list
+    equals the concatenation EXACTLY, the second crop's indices offset by the first crop's vertex count; the vertices
+    agree to 1e-4 index units after the shift (the gate of _check_surface; the shift changes the rounding of x + t) - on
+    the long axis of the second field to the spacing of fp32 at 4119, which is coarser than 1e-4."""
+    from humangaussian_amd.fields import marching_cubes
+    shape, boxes, centres = TWO_SPHERES[case]
+    assert np.prod(shape) > (1 << 20) and all(max(b - a for a, b in zip(lo, hi)) <= 32 for lo, hi in boxes)
+    field = _two_spheres(shape, boxes, centres)
+    thr = 0.25
+    v, t = marching_cubes(torch.as_tensor(field, device=DEV), thr)
+    parts = [marching_cubes(torch.as_tensor(np.ascontiguousarray(field[tuple(slice(a, b) for a, b in zip(lo, hi))]), device=DEV), thr)
+             for lo, hi in boxes]
+    (v1, t1), (v2, t2) = parts
+    assert len(v1) > 100 and len(v2) > 100 and len(t1) > 100 and len(t2) > 100
+    want_t = torch.cat([t1, t2 + len(v1)])
+    assert t.shape == want_t.shape and torch.equal(t, want_t)
+    want_v = torch.cat([v1 + torch.tensor(boxes[0][0], dtype=torch.float32, device=DEV),
+                        v2 + torch.tensor(boxes[1][0], dtype=torch.float32, device=DEV)])
+    # per axis: 1e-4, or where the coordinates are so large that fp32 is coarser than that (x up to 4119: spacing 2^-11)
+    # the two roundings by which the sides differ - x + t here, (x' + t) + shift there - of half a spacing each
+    tol = torch.tensor([max(1e-4, float(np.spacing(np.float32(n - 1)))) for n in shape], device=DEV)
+    assert v.shape == want_v.shape and ((v - want_v).abs().amax(0) <= tol).all(), (v - want_v).abs().amax(0)
+
+
 def test_marching_cubes_avatar_field_at_threshold_one():
     from humangaussian_amd.fields import extract_fields
     occ = extract_fields(_to_dev(_avatar(20000, 4)), 64, 16)[0]

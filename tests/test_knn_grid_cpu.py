@@ -3,35 +3,27 @@ cell of a point, shells of cells, the `reach` stop rule - checked against the br
 collinear, duplicated and outlier-stretched clouds: the stop rule must never end a search before the true three nearest
 neighbours have been seen.  (The HIP kernels themselves run in tests/test_gpu_api_contract.py against a k-d tree and against
 the brute-force kernel, bit for bit.)"""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gridfit_reference as G  # noqa: E402
 
 F = np.float32
 CELL_MAX = 4096
 
 
 def grid_setup(pts, nc_max):
-    P = len(pts)
+    """hgs_k_knn_grid_setup: the shared rule (gridfit_reference.py) behind knn.hip's own precondition and first cell edge"""
     lo = pts.min(0).astype(F)
     ext = (pts.max(0).astype(F) - lo).astype(F)
-    emax = F(ext.max())
-    h, g = F(1.0), np.ones(3, np.int64)
-    if emax > 0 and P > 8:
-        floor_ext = F(emax * F(1e-3))
-        vol = F(np.prod(np.maximum(ext, floor_ext).astype(F)))
-        h = F(np.cbrt(F(2.0) * vol / F(P)))
-        for _ in range(64):
-            c = np.floor(ext / h).astype(F) + F(1.0)
-            g = np.clip(c, 1, 4096).astype(np.int64)
-            if int(np.prod(g)) <= nc_max and np.all(ext / h < 4095.0):
-                break
-            h = F(h * F(1.26))
-    return lo, h, F(1.0) / h, g
+    return G.grid(lo, ext, G.h0_knn(ext, len(pts)) if len(pts) > 8 and ext.max() > 0 else None, nc_max)
 
 
-def cell_of(p, lo, inv_h, g):
-    c = np.floor(((p - lo).astype(F) * inv_h).astype(F))
-    return np.minimum(np.maximum(c, 0), (g - 1).astype(F)).astype(np.int64)
+cell_of = G.cell1
 
 
 def grid_knn(pts):

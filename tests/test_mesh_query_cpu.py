@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gridfit_reference as G  # noqa: E402
 import mesh_reference as R  # noqa: E402
 
 F32 = np.float32
@@ -70,9 +71,10 @@ def test_reference_skips_exactly_degenerate_faces():
 
 
 # ------------------------------------------------------------------------------------------------ grid restatement
-# The plan (hgs_k_mesh_bbox / _grid_setup / _count_refs) and the stop rule of mesh_grid_closest in numpy, fp32 where the
-# device uses fp32.  The union of the cell lists of a block of cells = the faces whose bounding-box cells overlap the block,
-# so a shell search is restated per face; after shell r the search stops when best d2 < reach^2 (margins as in mesh.hip).
+# The plan (hgs_k_mesh_bbox / _grid_setup / _count_refs: the grid rule itself is gridfit_reference.py's) and the stop rule
+# of mesh_grid_closest in numpy, fp32 where the device uses fp32.  The union of the cell lists of a block of cells = the
+# faces whose bounding-box cells overlap the block, so a shell search is restated per face; after shell r the search stops
+# when best d2 < reach^2 (margins as in mesh.hip).
 
 
 def plan(v, f):
@@ -80,27 +82,13 @@ def plan(v, f):
     fin = np.all(np.isfinite(v), axis=1)
     lo = v[fin].min(0)
     ext = (v[fin].max(0) - lo).astype(F32)
-    F = len(f)
-    nc_max = min(max(16 * F, 64), 1 << 22)
-    emax = F32(ext.max())
-    h, g = F32(1.0), np.ones(3, np.int64)
-    if emax > 0:
-        floor_ext = F32(emax * F32(1e-3))
-        vol = F32(F32(F32(max(ext[0], floor_ext)) * F32(max(ext[1], floor_ext))) * F32(max(ext[2], floor_ext)))
-        h = F32(np.cbrt(F32(vol / F32(8.0 * F))))
-        for _ in range(64):
-            c = np.floor((ext / h).astype(F32)) + 1
-            g = np.clip(c, 1, 4096).astype(np.int64)
-            if int(np.prod(g)) <= nc_max and np.all((ext / h).astype(F32) < 4095.0):
-                break
-            h = F32(h * F32(1.26))
-    inv_h = F32(F32(1.0) / h)
+    nc_max = min(max(16 * len(f), 64), 1 << 22)
+    lo, h, inv_h, g = G.grid(lo, ext, G.h0_mesh(ext, len(f)) if ext.max() > 0 else None, nc_max)
     ok = R.valid_faces(v, f)
     tri = v[f]                                             # (F, 3, 3)
 
     def cell(x):
-        c = np.floor(((x - lo).astype(F32) * inv_h).astype(F32))
-        return np.minimum(np.maximum(c, 0), (g - 1).astype(F32)).astype(np.int64)
+        return G.cell1(x, lo, inv_h, g)
     c0, c1 = cell(tri.min(1)), cell(tri.max(1))
     refs = int(np.prod(c1 - c0 + 1, axis=1)[ok].sum())
     cmax = F32(np.max(np.abs(np.stack([lo, (lo + (g * h).astype(F32)).astype(F32)]))))

@@ -3,7 +3,10 @@ gradient) of
   * forward + backward through the raw ABI on two single-view scenes (a small cloud with lists > 1024 entries: segments,
     transmittance products; a wider one), and
   * one batched call of 3 views of the small cloud through rasterize_gaussians_batch, forward + backward: the path of
-    calls of >= 3 views (hgs_k_sort_lds_ch, chunk-cell-major pair rows, hgs_k_pair_reduce_ch) that no single-view call takes.
+    calls of >= 3 views (hgs_k_sort_lds_ch, chunk-cell-major pair rows, hgs_k_pair_reduce_ch) that no single-view call takes, and
+  * the index builders beside the rasterizer, through the Python API (--save / --against only): distCUDA2 of a 100k-point
+    cloud, mesh build + query on the 20,480-face icosphere, the 64^3 density field of an avatar cloud in 16 blocks, marching
+    cubes of that field, prune_rows of 70,001 rows.
 
   python tools/cmp_variant.py variants/X/libhgs_rast.so [...]   raw-ABI cases: the in-tree build against every library given
   python tools/cmp_variant.py --save FILE                       all cases of THIS tree's build -> FILE (json)
@@ -73,6 +76,42 @@ def fingerprint_batch():
             ("batch3", "grads") + tuple(h(ins[k].grad) for k in names) + (h(m2.grad),)]
 
 
+def fingerprint_index():
+    """The k-NN grid, the mesh index, the density field, marching cubes and row compaction on fixed seeds: every quantity
+    they produce is an integer or comes from the same fp32 operations in any build that computes the same thing."""
+    import numpy as np
+    import mesh_reference as R
+    from humangaussian_amd import densify, synth
+    from humangaussian_amd.fields import extract_fields, marching_cubes
+    from humangaussian_amd.mesh import MeshIndex
+    from simple_knn._C import distCUDA2
+    dev = "cuda"
+    out = []
+    g = torch.Generator().manual_seed(3)
+    out.append(("knn", "distCUDA2_100k", h(distCUDA2((torch.randn(100_000, 3, generator=g) * 0.4).to(dev)))))
+    v, f = R.icosphere(5)
+    idx = MeshIndex(v, f)
+    rng = np.random.default_rng(4)
+    pts = torch.as_tensor(rng.uniform(-1.3, 1.3, (20_000, 3)).astype(np.float32), device=dev)
+    d, fc, uvw = idx.signed_distance(pts, return_uvw=True, mode="raystab")
+    out.append(("mesh", "icosphere5", tuple(int(x) for x in idx.grid_dims), int(idx.num_refs), h(d), h(fc), h(uvw)))
+    n = 20_000
+    rng = np.random.default_rng(4)
+    cloud = (synth.humanoid_points(n, seed=4).astype(np.float32), (0.002 + 0.95 * rng.uniform(size=(n, 1))).astype(np.float32),
+             (0.012 * np.exp(0.5 * rng.normal(size=(n, 3)))).astype(np.float32), rng.normal(size=(n, 4)).astype(np.float32))
+    res = extract_fields(tuple(torch.as_tensor(a, device=dev) for a in cloud), 64, 16, return_block_counts=True)
+    occ, counts = res[0], res[-1]
+    out.append(("field", "avatar_64_16", h(occ), h(counts)))
+    mv, mt = marching_cubes(occ, 1.0)
+    out.append(("mc", "avatar_64_16", tuple(mv.shape), tuple(mt.shape), h(mv), h(mt)))
+    P = 70_001
+    g = torch.Generator().manual_seed(2)
+    keep = (torch.rand(P, generator=g) < 0.6).to(dev)
+    rows = densify.prune_rows(keep, [torch.randn(P, 3, generator=g).to(dev), torch.randn(P, generator=g).to(dev)])
+    out.append(("prune_rows", "70001") + tuple(h(r) for r in rows))
+    return out
+
+
 def report(label, ref, got):
     ok = got == ref
     print(label, "IDENTICAL" if ok else "DIFFERENT")
@@ -99,7 +138,7 @@ if __name__ == "__main__":
     same = True
     if args.save or args.against:
         assert not args.libs, "library paths go with the raw-ABI mode only"
-        allfp = plain(ref + fingerprint_batch())
+        allfp = plain(ref + fingerprint_batch() + fingerprint_index())
         for r in allfp[len(ref):]:
             print("in-tree", tuple(r))
         if args.save:
