@@ -67,7 +67,7 @@ atexit.register(_dump_parity_log)
 
 def check_against_fp64_oracle(name, cloud, settings_fp32, hip, grads, img_tol=1e-4, grad_tol=1e-3,
                               cos_tol=1e-6, threads=None, minority_caps=True, gate_flip_images=True, raise_on_failure=True,
-                              grad_tol_by_key=None):
+                              grad_tol_by_key=None, refs=None):
     """BASELINE.json's parity bar at full size.  `hip` = (color, radii, depth, alpha, grads dict)
     on the CPU; `grads` = the three incoming gradients (or None: forward only).
 
@@ -95,24 +95,26 @@ def check_against_fp64_oracle(name, cloud, settings_fp32, hip, grads, img_tol=1e
     oracle included) is not within 1e-4 of an fp64 evaluation on every pixel of a million:
     ill-conditioned conics carry alpha errors of ~1e-4 relative; how far the fp32 oracle and this
     implementation each are from fp64 is recorded in the statistics (informational).
+    `refs` = (fp32, fp64) results of `oracle.forward_backward` for this cloud, settings and `grads`, where the caller has them
+    already (tests/test_gpu_list_boundaries.py: one pair per scene, shared); otherwise both are computed here.
     Returns the statistics (also appended to PARITY_LOG / $HGS_PARITY_STATS)."""
     import os
     import oracle
     if not torch.is_grad_enabled():          # the oracle differentiates with autograd
         with torch.enable_grad():
             return check_against_fp64_oracle(name, cloud, settings_fp32, hip, grads, img_tol, grad_tol, cos_tol, threads,
-                                             minority_caps, gate_flip_images, raise_on_failure, grad_tol_by_key)
+                                             minority_caps, gate_flip_images, raise_on_failure, grad_tol_by_key, refs)
     torch.set_num_threads(threads or max(1, min(os.cpu_count() or 1, 64)))
     c, r, d, a, g = hip
     st = settings_fp32
     H, W = int(st.image_height), int(st.image_width)
     zero = [torch.zeros(3, H, W), torch.zeros(1, H, W), torch.zeros(1, H, W)]
     args = (cloud.means3D, cloud.shs, None, cloud.opacities, cloud.scales, cloud.rotations, None, st)
-    o32 = oracle.forward_backward(*args, *(grads if grads is not None else zero), dtype=torch.float32,
-                                  want_means2D=grads is not None)
+    o32 = refs[0] if refs is not None else oracle.forward_backward(*args, *(grads if grads is not None else zero), dtype=torch.float32,
+                                                                   want_means2D=grads is not None)
     assert torch.equal(r, o32["radii"]), f"{name}: radii differ from the fp32 oracle"
-    o64 = oracle.forward_backward(*args, *(grads if grads is not None else zero), dtype=torch.float64,
-                                  want_means2D=grads is not None)
+    o64 = refs[1] if refs is not None else oracle.forward_backward(*args, *(grads if grads is not None else zero), dtype=torch.float64,
+                                                                   want_means2D=grads is not None)
     fragile = o32["fragile"]
     failures = []
 
