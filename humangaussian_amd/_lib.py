@@ -37,6 +37,27 @@ class HgsSettings(Structure):
     ]
 
 
+class HgsAdamTensor(Structure):
+    """ctypes mirror of `hgs_adam_tensor`."""
+    _fields_ = [
+        ("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+        ("rows", c_int64), ("row_floats", c_int32),
+        ("step_size", c_float), ("bc2_sqrt", c_float), ("w1", c_float), ("beta2", c_float), ("w2", c_float),
+        ("eps", c_float),
+    ]
+
+
+ADAM_MAX_TENSORS = 16
+
+
+class HgsAdamArgs(Structure):
+    """ctypes mirror of `hgs_adam_args` (the kernel argument of hgs_adam_step)."""
+    _fields_ = [
+        ("num_tensors", c_int32), ("visible_rows", c_int64), ("visible", c_void_p),
+        ("t", HgsAdamTensor * ADAM_MAX_TENSORS), ("block_start", c_uint32 * (ADAM_MAX_TENSORS + 1)),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -93,6 +114,7 @@ EXPORTS = {
     "hgs_compact_index": (ctypes.c_int, [c_int32] + [c_void_p] * 5),
     "hgs_gather_rows": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 4),
     "hgs_reanchor": (ctypes.c_int, [c_int32] + [c_void_p] * 7),
+    "hgs_adam_step": (ctypes.c_int, [POINTER(HgsAdamArgs), c_void_p]),
     "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -25,6 +25,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "mesh.hip"
 #include "fields.hip"
 #include "bookkeeping.hip"
+#include "optim.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -921,6 +922,38 @@ int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const i
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_reanchor, dim3((P + 255) / 256), dim3(256), 0, stream, (int)P, vertices, faces, mapping_face,
                      mapping_uvw, mapping_dist, xyz);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+// One launch for every tensor of the call (optim.hip): tensor k gets one workgroup per HGS_ADAM_BLOCK_ELEMS elements; beyond
+// HGS_ADAM_MAX_BLOCKS in all, every tensor's share shrinks in proportion (at least one) and its workgroups grid-stride.
+int hgs_adam_step(const hgs_adam_args* args, void* stream_) {
+  if (!args || args->num_tensors < 0 || args->num_tensors > HGS_ADAM_MAX_TENSORS) return HGS_EINVAL;
+  hgs_adam_args a = *args;
+  if (a.visible && a.visible_rows < 0) return HGS_EINVAL;
+  unsigned long long want[HGS_ADAM_MAX_TENSORS], total = 0;
+  for (int k = 0; k < a.num_tensors; ++k) {
+    const hgs_adam_tensor& t = a.t[k];
+    if (t.rows < 0 || t.row_floats < 0) return HGS_EINVAL;
+    if (t.row_floats > 0 && (unsigned long long)t.rows > (1ull << 62) / (unsigned long long)t.row_floats) return HGS_EINVAL;
+    if (a.visible && t.rows != a.visible_rows) return HGS_ESHAPE;
+    const unsigned long long n = (unsigned long long)t.rows * (unsigned long long)t.row_floats;
+    if (n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)) return HGS_EINVAL;
+    want[k] = (n + HGS_ADAM_BLOCK_ELEMS - 1) / HGS_ADAM_BLOCK_ELEMS;
+    total += want[k];
+  }
+  if (total == 0) return HGS_OK;
+  uint32_t start = 0;
+  for (int k = 0; k < a.num_tensors; ++k) {
+    a.block_start[k] = start;
+    unsigned long long nb = want[k];
+    if (total > HGS_ADAM_MAX_BLOCKS && nb > 0) nb = std::max<unsigned long long>(1, nb * HGS_ADAM_MAX_BLOCKS / total);
+    start += (uint32_t)nb;
+  }
+  for (int k = a.num_tensors; k <= HGS_ADAM_MAX_TENSORS; ++k) a.block_start[k] = start;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_adam, dim3(start), dim3(HGS_ADAM_THREADS), 0, stream, a);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

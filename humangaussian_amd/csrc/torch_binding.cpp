@@ -848,6 +848,73 @@ Tensor reanchor(const Tensor& vertices, const Tensor& faces, const Tensor& mappi
   return xyz;
 }
 
+// ---- the optimizer step (include/hgs_rast.h: hgs_adam_step): every tensor of the lists in one launch per
+// HGS_ADAM_MAX_TENSORS of them, on the current stream, nothing read back.  scalars[k] = the six floats of tensor k in the
+// header's order (step_size, bc2_sqrt, w1, beta2, w2, eps), derived by the caller in double.  Nothing is converted or
+// copied here: a tensor that is not fp32, contiguous and on the device of the first is an error (optim.py sends such
+// parameters down torch's own path instead).
+void adam_step(std::vector<Tensor> params, const std::vector<Tensor>& grads, std::vector<Tensor> exp_avgs,
+               std::vector<Tensor> exp_avg_sqs, const std::vector<std::vector<double>>& scalars,
+               const c10::optional<Tensor>& visible) {
+  at::NoGradGuard ng;
+  const size_t n = params.size();
+  if (grads.size() != n || exp_avgs.size() != n || exp_avg_sqs.size() != n || scalars.size() != n)
+    throw std::runtime_error("adam_step: params, grads, exp_avgs, exp_avg_sqs and scalars must have one entry per tensor");
+  if (n == 0) return;
+  const c10::Device dev = params[0].device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  const uint8_t* vis = nullptr;
+  int64_t vis_rows = 0;
+  Tensor vis_u8;
+  if (visible.has_value() && visible->defined()) {
+    if (visible->device() != dev || !visible->is_contiguous() ||
+        (visible->scalar_type() != at::kBool && visible->scalar_type() != at::kByte))
+      throw std::runtime_error("adam_step: visible must be a contiguous bool or uint8 tensor on " + dev.str());
+    vis_u8 = visible->scalar_type() == at::kBool ? visible->view(at::kByte) : *visible;      // (bool is one byte of 0 / 1)
+    vis_rows = vis_u8.numel();
+    if (vis_rows == 0) return;                       // no rows at all: nothing is visible
+    vis = vis_u8.data_ptr<uint8_t>();
+  }
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  for (size_t first = 0; first < n; first += HGS_ADAM_MAX_TENSORS) {
+    hgs_adam_args a{};
+    a.num_tensors = (int32_t)std::min<size_t>(HGS_ADAM_MAX_TENSORS, n - first);
+    a.visible = vis;
+    a.visible_rows = vis_rows;
+    for (int32_t j = 0; j < a.num_tensors; ++j) {
+      const size_t k = first + (size_t)j;
+      need_dev(params[k], dev, at::kFloat, "adam_step: param");
+      need_dev(grads[k], dev, at::kFloat, "adam_step: grad");
+      need_dev(exp_avgs[k], dev, at::kFloat, "adam_step: exp_avg");
+      need_dev(exp_avg_sqs[k], dev, at::kFloat, "adam_step: exp_avg_sq");
+      const int64_t numel = params[k].numel();
+      if (grads[k].numel() != numel || exp_avgs[k].numel() != numel || exp_avg_sqs[k].numel() != numel)
+        throw std::runtime_error("adam_step: a tensor's grad, exp_avg and exp_avg_sq must have its number of elements");
+      if (scalars[k].size() != 6) throw std::runtime_error("adam_step: six scalars per tensor");
+      hgs_adam_tensor& t = a.t[j];
+      t.rows = params[k].dim() >= 1 ? params[k].size(0) : 1;
+      const int64_t rf = t.rows > 0 ? numel / t.rows : 0;
+      if (rf > 0x7fffffffll) throw std::runtime_error("adam_step: rows of more than 2^31 - 1 elements are not supported");
+      t.row_floats = (int32_t)rf;
+      if (vis && t.rows != vis_rows)
+        throw std::runtime_error("adam_step: visible has " + std::to_string(vis_rows) + " entries, a tensor has " +
+                                 std::to_string(t.rows) + " rows");
+      t.param = fptr_mut(params[k]);
+      t.grad = fptr(grads[k]);
+      t.exp_avg = fptr_mut(exp_avgs[k]);
+      t.exp_avg_sq = fptr_mut(exp_avg_sqs[k]);
+      t.step_size = (float)scalars[k][0];
+      t.bc2_sqrt = (float)scalars[k][1];
+      t.w1 = (float)scalars[k][2];
+      t.beta2 = (float)scalars[k][3];
+      t.w2 = (float)scalars[k][4];
+      t.eps = (float)scalars[k][5];
+    }
+    check_rc(hgs_adam_step(&a, stream), "hgs_adam_step");
+  }
+}
+
 void set_stage_events(const c10::optional<std::vector<int64_t>>& fwd, const c10::optional<std::vector<int64_t>>& bwd) {
   g_stage_fwd.clear();
   g_stage_bwd.clear();
@@ -1072,6 +1139,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("densify_masks", &densify_masks, py::call_guard<py::gil_scoped_release>());
   m.def("compact_rows", &compact_rows, py::call_guard<py::gil_scoped_release>());
   m.def("reanchor", &reanchor, py::call_guard<py::gil_scoped_release>());
+  m.def("adam_step", &adam_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
+        py::arg("scalars"), py::arg("visible") = py::none(), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());

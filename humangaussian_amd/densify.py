@@ -13,7 +13,9 @@ elementwise kernels launched from Python:
 * `densify_and_prune`        <- gaussian_model.py:410-423 whole: the above + the sampling of the split children
                                 (:369-380) + the surgery on the Adam optimizer object (:283-357), on any object shaped like
                                 the reference GaussianModel; pinned to the reference's own method by
-                                tests/golden/reference_densify.npz (tests/golden/make_densify_fixture.py)."""
+                                tests/golden/reference_densify.npz (tests/golden/make_densify_fixture.py).
+* `prune_only`               <- gaussian_model.py:426-432 whole, through the same compaction; pinned by
+                                tests/golden/reference_prune_only.npz (tests/golden/make_prune_only_fixture.py)."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -81,6 +83,35 @@ def build_rotation(q: torch.Tensor) -> torch.Tensor:
                         2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
 
 
+def _compact_model(pc, keep: torch.Tensor, rows: dict, n_new: int, extras: Sequence[torch.Tensor] = ()):
+    """The compaction `densify_and_prune` and `prune_only` share: ONE `prune_rows` over `rows[attr]` (the six parameter
+    tensors, by attribute name), both Adam moments of each (padded with `n_new` zero rows: appended points start with zero
+    moments) and `extras`; then the optimizer surgery of `_prune_optimizer` (gaussian_model.py:283-299): new leaf
+    Parameters in the groups and on `pc`, the state re-keyed to them.  Returns the compacted `extras`."""
+    dev = keep.device
+    tensors, slots = [], []
+    for name, attr in _GROUPS:
+        group = next(g for g in pc.optimizer.param_groups if g["name"] == name)
+        assert len(group["params"]) == 1
+        st = pc.optimizer.state.get(group["params"][0], None)
+        tensors.append(rows[attr])
+        slots.append((group, attr, st))
+        if st is not None:
+            for m in ("exp_avg", "exp_avg_sq"):
+                pad = torch.zeros((n_new,) + tuple(st[m].shape[1:]), dtype=st[m].dtype, device=dev)
+                tensors.append(torch.cat((st[m], pad), dim=0) if n_new else st[m])
+    out = iter(prune_rows(keep, tensors + list(extras)))
+    for group, attr, st in slots:
+        new = torch.nn.Parameter(next(out).requires_grad_(True))
+        if st is not None:
+            st["exp_avg"], st["exp_avg_sq"] = next(out), next(out)
+            del pc.optimizer.state[group["params"][0]]
+            pc.optimizer.state[new] = st
+        group["params"][0] = new
+        setattr(pc, attr, new)
+    return list(out)
+
+
 def densify_and_prune(pc, max_grad: float, min_opacity: float, extent: float, max_screen_size: Optional[float],
                       N: int = 2, split_samples: Optional[torch.Tensor] = None):
     """`GaussianModel.densify_and_prune(max_grad, min_opacity, extent, max_screen_size)` of
@@ -129,28 +160,28 @@ def densify_and_prune(pc, max_grad: float, min_opacity: float, extent: float, ma
     keep = ~prune
     keep[:P] &= ~split                                                          # the split parents go (:390-391)
     # ---- one compaction for the parameters and both Adam moments (appended rows start with zero moments: :346-347)
-    tensors, slots = [], []
-    for name, attr in _GROUPS:
-        group = next(g for g in pc.optimizer.param_groups if g["name"] == name)
-        assert len(group["params"]) == 1
-        st = pc.optimizer.state.get(group["params"][0], None)
-        tensors.append(grown[attr])
-        slots.append((group, attr, st))
-        if st is not None:
-            for m in ("exp_avg", "exp_avg_sq"):
-                pad = torch.zeros((n_all - P,) + tuple(st[m].shape[1:]), dtype=st[m].dtype, device=dev)
-                tensors.append(torch.cat((st[m], pad), dim=0))
-    out = iter(prune_rows(keep, tensors))
-    for group, attr, st in slots:
-        new = torch.nn.Parameter(next(out).requires_grad_(True))
-        if st is not None:
-            st["exp_avg"], st["exp_avg_sq"] = next(out), next(out)
-            del pc.optimizer.state[group["params"][0]]
-            pc.optimizer.state[new] = st
-        group["params"][0] = new
-        setattr(pc, attr, new)
+    _compact_model(pc, keep, grown, n_all - P)
     n_final = pc._xyz.shape[0]
     pc.xyz_gradient_accum = torch.zeros((n_final, 1), device=dev)                # (:354-357 zero them; pruning zeros keeps zeros)
     pc.denom = torch.zeros((n_final, 1), device=dev)
     pc.max_radii2D = torch.zeros((n_final,), device=dev)
     return {"cloned": nc, "split": ns, "children": N * ns, "pruned": int(n_all - ns - n_final), "points": n_final}
+
+
+def prune_only(pc, min_opacity: float = 0.005, size_thresh: float = 0.01):
+    """`GaussianModel.prune_only(min_opacity, size_thresh)` of gaussiansplatting/scene/gaussian_model.py:426-432 whole, on
+    the same kind of object as `densify_and_prune`: prune where `get_opacity < min_opacity` or the largest `get_scaling`
+    exceeds `size_thresh` (one mask pass on the raw parameters), then `prune_points` (:301-315) - every parameter, both
+    Adam moments and the three statistics (which keep their values here: nothing re-zeroes them) through the compaction
+    `densify_and_prune` uses, survivors in their order.  Returns a dict of counts."""
+    if not size_thresh > 0:
+        raise ValueError("prune_only: size_thresh must be positive")
+    P = pc._xyz.shape[0]
+    _, _, prune, _ = densify_masks(pc.xyz_gradient_accum, pc.denom, pc._scaling, pc._opacity, pc.max_radii2D, 0.0,
+                                   0.0, 1.0, min_opacity, max_screen_size=None, size_thresh=size_thresh,
+                                   raw_params=True)
+    rows = {attr: getattr(pc, attr).detach() for _, attr in _GROUPS}
+    pc.xyz_gradient_accum, pc.denom, pc.max_radii2D = _compact_model(
+        pc, ~prune, rows, 0, (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D))
+    n_final = pc._xyz.shape[0]
+    return {"pruned": P - n_final, "points": n_final}

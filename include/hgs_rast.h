@@ -368,6 +368,42 @@ int hgs_gather_rows(int64_t n_out, int32_t row_floats, const int32_t* src_of_dst
 int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const int32_t* mapping_face,
                  const float* mapping_uvw, const float* mapping_dist, float* xyz, void* stream);
 
+/* ---- the optimizer step: Adam over every parameter tensor of the model in ONE launch -------------------------------
+ * The reference builds torch.optim.Adam over six groups of one tensor each (gaussiansplatting/scene/gaussian_model.py:
+ * 156-165): a chain of elementwise kernels per group and step.  hgs_adam_step updates up to HGS_ADAM_MAX_TENSORS tensors
+ * in one launch; the struct below travels by value as the kernel's argument (no device-side table, no H2D copy).
+ * Per tensor: param / exp_avg / exp_avg_sq (updated in place) and grad, fp32, contiguous, rows x row_floats elements, and
+ * the fp32 scalars the HOST derives in double from the group's lr, betas, eps and the step count t (after its increment):
+ *   step_size = lr / (1 - beta1^t),  bc2_sqrt = sqrt(1 - beta2^t),  w1 = 1 - beta1,  beta2,  w2 = 1 - beta2,  eps.
+ * Per element, each operation rounded to fp32 in this order (no contraction):
+ *   m = m + (g - m) * w1;   v = v * beta2 + (g * g) * w2;   d = sqrtf(v) / bc2_sqrt + eps;   p = p - step_size * (m / d)
+ * (torch.optim.Adam's non-fused, non-capturable step without weight decay, amsgrad or maximize).
+ * visible (optional, uint8 [visible_rows]): only elements of rows r with visible[r] != 0 are touched; the param, exp_avg
+ * and exp_avg_sq of every other row keep their bits.  Every tensor of the call must then have visible_rows rows
+ * (HGS_ESHAPE otherwise).  The scalars stay those of the global step count.
+ * Tensors whose four pointers are 16-byte aligned move in 16-byte accesses, others element by element (same values).
+ * block_start is filled by hgs_adam_step (the caller's content is ignored).
+ * Returns HGS_EINVAL for args == NULL, num_tensors outside [0, HGS_ADAM_MAX_TENSORS], negative rows / row_floats or a NULL
+ * pointer of a tensor that has elements; zero tensors or zero elements: HGS_OK without a launch. */
+#define HGS_ADAM_MAX_TENSORS 16
+typedef struct hgs_adam_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t rows;
+  int32_t row_floats;
+  float step_size, bc2_sqrt, w1, beta2, w2, eps;
+} hgs_adam_tensor;
+typedef struct hgs_adam_args {
+  int32_t num_tensors;
+  int64_t visible_rows;          /* read only when visible != NULL */
+  const uint8_t* visible;
+  hgs_adam_tensor t[HGS_ADAM_MAX_TENSORS];
+  uint32_t block_start[HGS_ADAM_MAX_TENSORS + 1];   /* workgroups of tensor k: [block_start[k], block_start[k + 1]) */
+} hgs_adam_args;
+int hgs_adam_step(const hgs_adam_args* args, void* stream);
+
 /* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
  * The per-avatar anchoring of /root/reference/animation.py:333-378:
  *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
