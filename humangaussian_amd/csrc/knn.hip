@@ -2,7 +2,9 @@
 // `simple_knn._C.distCUDA2` the reference calls when it creates a cloud from a point set
 // (/root/reference/gaussiansplatting/scene/gaussian_model.py:134, gs_renderer.py:386-389;
 // semantics in submodules/simple-knn/simple_knn.cu:147-183: neighbours exclude the point's own
-// INDEX, duplicates at distance 0 count, result = (d0 + d1 + d2) / 3 with d0 <= d1 <= d2).
+// INDEX, duplicates at distance 0 count, result = (d0 + d1 + d2) / 3 with d0 <= d1 <= d2; a candidate at a NaN or infinite
+// distance fails upstream's `knn[j] > dist` and is ignored; a slot no neighbour fills holds FLT_MAX, so a point with fewer
+// than three finite-distance neighbours - a point with a non-finite coordinate has none - gets FLT_MAX / 3 or +inf).
 //
 // Upstream sorts the points by Morton code (a global radix sort) and prunes 1024-point boxes
 // (simple_knn.cu:63-221).  Here, MI355X-first, without a global sort and without a host round trip:
@@ -33,6 +35,17 @@ struct KnnGrid {
   uint32_t brute;                      // 1: degenerate -> brute force
   uint32_t pad;
 };
+
+// A point with a NaN or an infinite coordinate is at no finite distance from anything: it is nobody's neighbour and has none.
+// The branch-free insert of both searches orders with fminf / fmaxf, which DROP a NaN: a NaN distance would go in as a second
+// copy of the nearest one.  So no NaN distance is ever formed: as a CANDIDATE such a point is moved to (+inf, +inf, +inf),
+// as a QUERY it is answered without a search (grid) or moved to (-inf, -inf, -inf) (brute force) - every difference is then
+// finite or +inf, never inf - inf, and a distance of +inf passes through the insert without a trace (every slot is <=
+// FLT_MAX).  The inner loops pay nothing for it.
+__device__ __forceinline__ bool knn_finite(float x, float y, float z) {
+  const float big = 3.402823466e+38f;
+  return fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big;
+}
 
 extern "C" __global__ void __launch_bounds__(256)
 hgs_k_knn_bbox(int P, const float* __restrict__ pts, KnnGrid* __restrict__ G) {
@@ -116,7 +129,9 @@ hgs_k_knn_scatter(int P, const float* __restrict__ pts, const uint32_t* __restri
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
   const uint32_t slot = atomicAdd(&cursor[cell_of[i]], 1u);
-  sorted[slot] = make_float4(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], __uint_as_float((uint32_t)i));
+  float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+  if (!knn_finite(x, y, z)) x = y = z = INFINITY;      // (stays in the cell it was counted in; a candidate at +inf from everyone)
+  sorted[slot] = make_float4(x, y, z, __uint_as_float((uint32_t)i));
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -128,6 +143,7 @@ hgs_k_knn_search(int P, const KnnGrid* __restrict__ Gp, const uint32_t* __restri
   if (t >= P) return;
   const float4 me = sorted[t];
   const uint32_t self = __float_as_uint(me.w);
+  if (me.x == INFINITY) { out[self] = INFINITY; return; }      // a non-finite point (hgs_k_knn_scatter): three empty slots
   int cx, cy, cz;
   knn_cell_of(G, me.x, me.y, me.z, cx, cy, cz);
   const float big = 3.402823466e+38f;
@@ -192,14 +208,17 @@ hgs_k_knn3(int P, const float* __restrict__ pts, float* __restrict__ out, const 
   const int i = blockIdx.x * 256 + tid;
   float px = 0.f, py = 0.f, pz = 0.f;
   if (i < P) { px = pts[3 * (size_t)i]; py = pts[3 * (size_t)i + 1]; pz = pts[3 * (size_t)i + 2]; }
+  if (!knn_finite(px, py, pz)) px = py = pz = -INFINITY;      // a non-finite query: +inf from every candidate
   const float big = 3.402823466e+38f;
   float b0 = big, b1 = big, b2 = big;
   for (int base = 0; base < P; base += HGS_KNN_TILE) {
 #pragma unroll
     for (int k = tid; k < HGS_KNN_TILE; k += 256) {
       const int j = base + k;
-      tile[k] = (j < P) ? make_float4(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], 0.f)
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (j < P) q = make_float4(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], 0.f);
+      if (!knn_finite(q.x, q.y, q.z)) q.x = q.y = q.z = INFINITY;      // a non-finite candidate
+      tile[k] = q;
     }
     __syncthreads();
     const int cnt = min(HGS_KNN_TILE, P - base);

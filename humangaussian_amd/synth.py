@@ -166,6 +166,11 @@ def mean_knn_dist2(points: np.ndarray, k: int = 3) -> np.ndarray:
     """Mean squared distance to the k nearest neighbours (what simple_knn.distCUDA2
     returns, `submodules/simple-knn/simple_knn.cu:147-183`)."""
     from scipy.spatial import cKDTree
+    ok = np.isfinite(points).all(1)
+    if not ok.all():      # a point with a NaN / inf coordinate is nobody's neighbour and has none (csrc/knn.hip): +inf
+        out = np.full(len(points), np.inf, np.float32)
+        out[ok] = mean_knn_dist2(points[ok], k)
+        return out
     d, _ = cKDTree(points).query(points, k=k + 1)
     return (d[:, 1:] ** 2).mean(1).astype(np.float32)
 
