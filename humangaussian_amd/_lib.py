@@ -58,6 +58,22 @@ class HgsAdamArgs(Structure):
     ]
 
 
+class HgsLbsArgs(Structure):
+    """ctypes mirror of `hgs_lbs_args` (hgs_lbs_pose)."""
+    _fields_ = [
+        ("V", c_int32), ("J", c_int32), ("F", c_int32), ("K", c_int32),
+        ("weight_width", c_int32), ("posedirs_stride", c_int32),
+        ("v_shaped", c_void_p), ("J_rest", c_void_p), ("parents", c_void_p), ("posedirs", c_void_p),
+        ("weight_joint", c_void_p), ("weight_value", c_void_p), ("poses", c_void_p), ("transl", c_void_p),
+        ("centre", c_float * 3), ("scale", c_float),
+        ("workspace", c_void_p), ("vertices", c_void_p), ("joints", c_void_p),
+    ]
+
+
+LBS_MAX_JOINTS = 64
+LBS_FRAME_TILE = 8
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -115,6 +131,8 @@ EXPORTS = {
     "hgs_gather_rows": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 4),
     "hgs_reanchor": (ctypes.c_int, [c_int32] + [c_void_p] * 7),
     "hgs_adam_step": (ctypes.c_int, [POINTER(HgsAdamArgs), c_void_p]),
+    "hgs_lbs_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "hgs_lbs_pose": (ctypes.c_int, [POINTER(HgsLbsArgs), c_void_p]),
     "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -141,6 +141,52 @@ class MotionDriver:
         return v
 
 
+class SMPLXDriver:
+    """Posed body-mesh vertices per frame from the body model itself: `body` is a `body.SkinnedBody` (for the reference: the
+    SMPL-X model file, `SkinnedBody.from_smplx_npz`), `poses` a clip (F, J, 3) of axis-angle joint rotations (AMASS: the
+    `poses` of the .npz, reshaped to (F, 55, 3)).  The interface `AvatarAnimator` takes from `MotionDriver`: `vertices(i)`,
+    `num_poses`, `source`; frame i uses pose i mod F.
+
+    body_only=True is the reference (animation.py:216, :292-303): `poses[:, 1:22]` drive joints 1-21, global orientation,
+    jaw, eyes and hands stay zero.  body_only=False uses every joint of the clip as given.
+    The recentring of animation.py:321-330 is part of every call: centre = the middle of the ZERO-pose vertices' box,
+    scale = 0.6 / its largest side, times 1.1 ** 10; both are fixed at construction (the reference fixes them at its first
+    forward).  `vertices(i)` is one `body.pose` call, `precompute(frames)` one batched call."""
+
+    def __init__(self, body, poses, body_only: bool = True, source: str = "SMPL-X clip"):
+        self.body, self.body_only, self.source = body, bool(body_only), source
+        self.device = body.device
+        p = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
+        p = np.asarray(p, np.float32).reshape(p.shape[0], -1, 3)
+        J = body.num_joints
+        if p.shape[0] < 1 or p.shape[1] < min(J, 22 if body_only else J):
+            raise ValueError(f"poses must be (F >= 1, {J}, 3), got {p.shape}")
+        full = np.zeros((p.shape[0], J, 3), np.float32)
+        if body_only:
+            hi = min(22, J)
+            full[:, 1:hi] = p[:, 1:hi]
+        else:
+            full[:] = p[:, :J]
+        self.poses = torch.from_numpy(full).to(self.device)
+        self.num_poses = int(full.shape[0])
+        rest = body.pose(np.zeros((J, 3), np.float32))[0]
+        vmin, vmax = rest.min(0).values.cpu().numpy().astype(np.float32), rest.max(0).values.cpu().numpy().astype(np.float32)
+        self.centre = (vmax + vmin) / 2
+        self.scale = float(0.6 / np.max(vmax - vmin)) * 1.1 ** 10
+
+    def vertices(self, i: int) -> torch.Tensor:
+        return self.body.pose(self.poses[i % self.num_poses], centre=self.centre, scale=self.scale)[0]
+
+    def rest_vertices(self) -> torch.Tensor:
+        """(V, 3): the zero pose under the driver's affine - the mesh a trained avatar is anchored on (animation.py:333-345)"""
+        return self.body.pose(torch.zeros_like(self.poses[0]), centre=self.centre, scale=self.scale)[0]
+
+    def precompute(self, frames: Sequence[int]) -> torch.Tensor:
+        """(len(frames), V, 3): the frames of the list in ONE call; row k has the bits of `vertices(frames[k])`"""
+        idx = torch.as_tensor([int(i) % self.num_poses for i in frames], dtype=torch.long, device=self.device)
+        return self.body.pose(self.poses.index_select(0, idx), centre=self.centre, scale=self.scale)
+
+
 def human_mesh_anchors(n: int, seed: int = 0, device="cuda", max_dist: float = 0.004):
     """The body mesh (`synth.human_mesh()`: the reference's human.obj where the local asset exists, the procedural capsule
     mesh otherwise) + n Gaussians anchored on it the way animation.py:339-345 anchors a trained avatar: a face, barycentric

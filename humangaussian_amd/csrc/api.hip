@@ -26,6 +26,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "fields.hip"
 #include "bookkeeping.hip"
 #include "optim.hip"
+#include "lbs.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -954,6 +955,39 @@ int hgs_adam_step(const hgs_adam_args* args, void* stream_) {
   for (int k = a.num_tensors; k <= HGS_ADAM_MAX_TENSORS; ++k) a.block_start[k] = start;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_adam, dim3(start), dim3(HGS_ADAM_THREADS), 0, stream, a);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+size_t hgs_lbs_workspace_bytes(int32_t J, int32_t F) {
+  if (J < 1 || J > HGS_LBS_MAX_JOINTS || F < 0) return 0;
+  return hgs_align_up(((size_t)F * J * 15 + (size_t)F * 9 * (J - 1)) * sizeof(float), 256);
+}
+
+// Two launches (lbs.hip): one wave per frame for the joints, then one workgroup per (64 vertices, tile of frames).
+int hgs_lbs_pose(const hgs_lbs_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_lbs_args& a = *args;
+  if (a.J < 1 || a.J > HGS_LBS_MAX_JOINTS || a.V < 0 || a.V > (1 << 29) || a.F < 0) return HGS_EINVAL;
+  if (a.K != 0 && a.K != 9 * (a.J - 1)) return HGS_EINVAL;
+  if (a.weight_width < 1 || a.weight_width > a.J) return HGS_EINVAL;
+  if (a.F == 0 || a.V == 0) return HGS_OK;
+  if (!a.v_shaped || !a.J_rest || !a.parents || !a.weight_joint || !a.weight_value || !a.poses || !a.workspace || !a.vertices)
+    return HGS_EINVAL;
+  if (a.K > 0) {
+    const long long need = 12ll * ((a.V + 3) / 4);
+    if (!a.posedirs || ((uintptr_t)a.posedirs & 15) || (a.posedirs_stride & 3) || a.posedirs_stride < need) return HGS_EINVAL;
+  }
+  if ((uintptr_t)a.workspace & 15) return HGS_EINVAL;
+  const bool one = a.F == 1;
+  const unsigned long long tiles = one ? 1ull : ((unsigned long long)a.F + HGS_LBS_FRAME_TILE - 1) / HGS_LBS_FRAME_TILE;
+  const unsigned long long blocks = tiles * (unsigned long long)((a.V + HGS_LBS_VERTS - 1) / HGS_LBS_VERTS);
+  if (blocks > 0x7fffffffull) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_lbs_joints, dim3((unsigned)a.F), dim3(64), 0, stream, a);
+  HGS_LAUNCH_CHECK();
+  if (one) hipLaunchKernelGGL(hgs_k_lbs_skin_f1, dim3((unsigned)blocks), dim3(HGS_LBS_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL(hgs_k_lbs_skin_f8, dim3((unsigned)blocks), dim3(HGS_LBS_THREADS), 0, stream, a);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -915,6 +915,71 @@ void adam_step(std::vector<Tensor> params, const std::vector<Tensor>& grads, std
   }
 }
 
+// ---- posing a skinned body (include/hgs_rast.h: hgs_lbs_pose): F frames in two launches on the current stream, the
+// workspace from the caching allocator, nothing read back.  Every tensor is what body.SkinnedBody keeps resident: fp32 /
+// int32, contiguous, on one device - nothing is converted or copied here.  posedirs is the padded (K, stride) table or
+// None (K = 0).  Returns (vertices (F, V, 3), joints (F, J, 3) or None).
+std::tuple<Tensor, c10::optional<Tensor>> lbs_pose(const Tensor& v_shaped, const Tensor& J_rest, const Tensor& parents,
+                                                   const c10::optional<Tensor>& posedirs, const Tensor& weight_joint,
+                                                   const Tensor& weight_value, const Tensor& poses,
+                                                   const c10::optional<Tensor>& transl, std::vector<double> centre, double scale,
+                                                   bool return_joints) {
+  at::NoGradGuard ng;
+  const c10::Device dev = poses.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(v_shaped, dev, at::kFloat, "lbs_pose: v_shaped");
+  need_dev(J_rest, dev, at::kFloat, "lbs_pose: J_rest");
+  need_dev(parents, dev, at::kInt, "lbs_pose: parents");
+  need_dev(weight_joint, dev, at::kInt, "lbs_pose: weight_joint");
+  need_dev(weight_value, dev, at::kFloat, "lbs_pose: weight_value");
+  need_dev(poses, dev, at::kFloat, "lbs_pose: poses");
+  if (poses.dim() != 3 || poses.size(2) != 3) throw std::runtime_error("lbs_pose: poses must be (F, J, 3)");
+  const int64_t F = poses.size(0), J = poses.size(1), V = v_shaped.numel() / 3;
+  if (J < 1 || J > HGS_LBS_MAX_JOINTS)
+    throw std::runtime_error("lbs_pose: 1.." + std::to_string(HGS_LBS_MAX_JOINTS) + " joints, got " + std::to_string(J));
+  if (v_shaped.numel() != 3 * V || J_rest.numel() != 3 * J || parents.numel() != J || V > (1 << 29) || F > 0x7fffffffll)
+    throw std::runtime_error("lbs_pose: v_shaped (V, 3), J_rest (J, 3) and parents (J,) do not fit poses (F, J, 3)");
+  if (weight_joint.dim() != 2 || weight_joint.size(0) != V || weight_value.sizes() != weight_joint.sizes())
+    throw std::runtime_error("lbs_pose: weight_joint and weight_value must both be (V, width)");
+  if (centre.size() != 3) throw std::runtime_error("lbs_pose: centre has three components");
+  hgs_lbs_args a{};
+  a.V = (int32_t)V; a.J = (int32_t)J; a.F = (int32_t)F;
+  a.weight_width = (int32_t)std::min<int64_t>(weight_joint.size(1), 0x7fffffffll);
+  if (posedirs.has_value() && posedirs->defined() && posedirs->numel() > 0) {
+    need_dev(*posedirs, dev, at::kFloat, "lbs_pose: posedirs");
+    if (posedirs->dim() != 2 || posedirs->size(0) != 9 * (J - 1) || posedirs->size(1) > 0x7fffffffll)
+      throw std::runtime_error("lbs_pose: posedirs must be (9 (J - 1), stride)");
+    a.K = (int32_t)posedirs->size(0);
+    a.posedirs_stride = (int32_t)posedirs->size(1);
+    a.posedirs = fptr(*posedirs);
+  }
+  if (transl.has_value() && transl->defined()) {
+    need_dev(*transl, dev, at::kFloat, "lbs_pose: transl");
+    if (transl->numel() != 3 * F) throw std::runtime_error("lbs_pose: transl must be (F, 3)");
+    a.transl = fptr(*transl);
+  }
+  Tensor vertices = at::empty({F, V, 3}, poses.options());
+  Tensor joints;
+  if (return_joints) joints = at::empty({F, J, 3}, poses.options());
+  Tensor work = at::empty({(int64_t)hgs_lbs_workspace_bytes((int32_t)J, (int32_t)F)}, at::TensorOptions().dtype(at::kByte).device(dev));
+  a.v_shaped = fptr(v_shaped);
+  a.J_rest = fptr(J_rest);
+  a.parents = parents.data_ptr<int32_t>();
+  a.weight_joint = V > 0 ? weight_joint.data_ptr<int32_t>() : nullptr;
+  a.weight_value = fptr(weight_value);
+  a.poses = fptr(poses);
+  for (int c = 0; c < 3; ++c) a.centre[c] = (float)centre[c];
+  a.scale = (float)scale;
+  a.workspace = work.numel() ? work.data_ptr() : nullptr;
+  a.vertices = fptr_mut(vertices);
+  a.joints = return_joints ? fptr_mut(joints) : nullptr;
+  check_rc(hgs_lbs_pose(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_lbs_pose");
+  if (return_joints && V == 0 && F > 0)
+    throw std::runtime_error("lbs_pose: joints of a body without vertices are not computed");
+  return {vertices, return_joints ? c10::optional<Tensor>(joints) : c10::nullopt};
+}
+
 void set_stage_events(const c10::optional<std::vector<int64_t>>& fwd, const c10::optional<std::vector<int64_t>>& bwd) {
   g_stage_fwd.clear();
   g_stage_bwd.clear();
@@ -1141,6 +1206,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reanchor", &reanchor, py::call_guard<py::gil_scoped_release>());
   m.def("adam_step", &adam_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
         py::arg("scalars"), py::arg("visible") = py::none(), py::call_guard<py::gil_scoped_release>());
+  m.def("lbs_pose", &lbs_pose, py::arg("v_shaped"), py::arg("J_rest"), py::arg("parents"), py::arg("posedirs"),
+        py::arg("weight_joint"), py::arg("weight_value"), py::arg("poses"), py::arg("transl") = py::none(),
+        py::arg("centre") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("scale") = 1.0, py::arg("return_joints") = false,
+        py::call_guard<py::gil_scoped_release>());
   m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());

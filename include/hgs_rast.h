@@ -404,6 +404,61 @@ typedef struct hgs_adam_args {
 } hgs_adam_args;
 int hgs_adam_step(const hgs_adam_args* args, void* stream);
 
+/* ---- posing a skinned body: linear blend skinning (the reference's per-frame SMPL-X forward) --------------------------
+ * /root/reference/animation.py:552-556 -> load_smplx (:273-330) runs the `smplx` package's forward on the CPU for every
+ * frame, copies the vertices to numpy and recentres / rescales them (:320-330).  [UPSTREAM-KNOWLEDGE] the computation is
+ * that package's lbs(); it is not in the reference tree.  hgs_lbs_pose poses F frames of one body in two launches.
+ * Sizes: V vertices; J joints (1 <= J <= HGS_LBS_MAX_JOINTS) with parents[0] = -1 and parents[j] < j (the HOST's check: the
+ * kernels trust it, a broken table leaves joints at their local transform but reads nothing out of bounds);
+ * K = 9 (J - 1) rows of pose blend shapes, or K = 0 for a body without them; F frames.
+ * Per frame, every operation rounded to fp32 (no contraction), 3-term dot products as (a0 b0 + a1 b1) + a2 b2:
+ *   - R_j from the axis-angle a_j = poses[f][j]: angle = |a + 1e-8|, k = a / angle, R = I + sin(angle) [k]x +
+ *     (1 - cos(angle)) [k]x^2 (the package's batch_rodrigues: a zero pose gives R = I exactly, never a NaN);
+ *   - pf = concat over j >= 1 of (R_j - I), row-major;  v_posed = v_shaped + sum_k pf[k] posedirs[k];
+ *   - G_0 = [R_0 | J_0], G_j = G_parent [R_j | J_j - J_parent];  posed joint j = G_j.t;  A_j = [G_j.R | G_j.t - G_j.R J_j];
+ *   - v = sum over the vertex's weight list, in list order, of w (A_j.R v_posed + A_j.t);
+ *   - vertices[f][v] = ((v + transl[f]) - centre) * scale, joints[f][j] = ((G_j.t + transl[f]) - centre) * scale.
+ * The sum over k is partitioned: row k belongs to slice k mod 32; a slice adds its rows in ascending k, the 32 slice sums
+ * are added in a fixed tree.  No atomics: a call is bit-reproducible, and frame f of a call with F > 1 has the bits of a
+ * call with that frame alone (frames are taken in tiles of HGS_LBS_FRAME_TILE, which share every load of posedirs).
+ * Arrays: v_shaped [V][3], J_rest [J][3], parents [J] int32, poses [F][J][3], transl [F][3] or NULL, vertices [F][V][3]
+ * (out), joints [F][J][3] (out) or NULL.
+ * posedirs [K][posedirs_stride] fp32: row k holds the 3 V values of blend shape k, then padding; posedirs_stride is a
+ * multiple of 4 and >= 12 ceil(V / 4), the pointer 16-byte aligned (every lane loads 16 bytes).  The padding is read
+ * and ignored.  posedirs may be NULL when K = 0.
+ * Skinning weights: the dense V x J matrix packed on the host into weight_width slots per vertex, weight_joint
+ * [V][weight_width] int32 and weight_value [V][weight_width] fp32, joints ascending, unused slots (joint 0, weight 0);
+ * 1 <= weight_width <= J (the most non-zeros of any vertex: nothing is dropped).  A joint index outside [0, J) is
+ * clamped into it.
+ * workspace: hgs_lbs_workspace_bytes(J, F) bytes (0 for J or F out of range), 16-byte aligned; after the call it holds
+ * A [F][J][12] (rows of [R | t]), the posed joints [F][J][3] before transl and the affine, and pf [F][9 (J - 1)].
+ * Returns HGS_EINVAL without a launch for args == NULL, J outside [1, HGS_LBS_MAX_JOINTS], negative V or F, V > 2^29,
+ * K other than 0 or 9 (J - 1), weight_width outside [1, J], a posedirs_stride or alignment other than the above, or a
+ * NULL pointer for an array that has elements; F == 0 or V == 0: HGS_OK without a launch.
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_LBS_MAX_JOINTS 64
+#define HGS_LBS_FRAME_TILE 8
+typedef struct hgs_lbs_args {
+  int32_t V, J, F, K;
+  int32_t weight_width;
+  int32_t posedirs_stride;       /* floats per row of posedirs (read only when K > 0) */
+  const float* v_shaped;
+  const float* J_rest;
+  const int32_t* parents;
+  const float* posedirs;
+  const int32_t* weight_joint;
+  const float* weight_value;
+  const float* poses;
+  const float* transl;           /* or NULL */
+  float centre[3];
+  float scale;
+  void* workspace;
+  float* vertices;
+  float* joints;                 /* or NULL */
+} hgs_lbs_args;
+size_t hgs_lbs_workspace_bytes(int32_t J, int32_t F);
+int hgs_lbs_pose(const hgs_lbs_args* args, void* stream);
+
 /* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
  * The per-avatar anchoring of /root/reference/animation.py:333-378:
  *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
