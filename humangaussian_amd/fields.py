@@ -46,10 +46,11 @@ def extract_fields(model_or_tensors, resolution: int = 128, num_blocks: int = 16
     No Gaussian above the opacity cut: a zero field, center 0 and scale 1.  Finding that out takes the plan's four small
     kernels and its one host wait (the filter runs on the device); only the lists and the evaluation are not launched.
     With no Gaussian at all (P == 0) nothing is launched."""
-    block_size = 2 / num_blocks
-    assert resolution % block_size == 0
+    if num_blocks < 1:
+        raise ValueError(f"extract_fields: num_blocks ({num_blocks}) must be at least 1")
     if resolution % num_blocks != 0:
         raise ValueError(f"extract_fields: resolution ({resolution}) must be a multiple of num_blocks ({num_blocks})")
+    block_size = 2 / num_blocks
     (xyz, opacity, scaling, rotation), is_model = _model_tensors(model_or_tensors)
     _check_device((xyz, opacity, scaling, rotation), "extract_fields")
     dev = xyz.device

@@ -289,10 +289,15 @@ def test_python_surface_without_a_gpu():
         fields.marching_cubes(torch.zeros(4, 4, 4), 0.5)
     with pytest.raises(RuntimeError, match="HIP device"):
         fields.extract_mesh(cpu)
-    with pytest.raises(AssertionError):                             # the reference's assertion: resolution % (2 / num_blocks)
+    # the rule is the integer one; the reference's float assertion (resolution % (2 / num_blocks) == 0) refused (33, 3)
+    with pytest.raises(RuntimeError, match="HIP device"):
         fields.extract_fields(cpu, resolution=33, num_blocks=3)
     with pytest.raises(ValueError, match="multiple of num_blocks"):
         fields.extract_fields(cpu, resolution=100, num_blocks=16)
+    with pytest.raises(ValueError, match="multiple of num_blocks"):
+        fields.extract_fields(cpu, resolution=33, num_blocks=2)
+    with pytest.raises(ValueError, match="at least 1"):
+        fields.extract_fields(cpu, resolution=32, num_blocks=0)
 
 
 def test_c_surface_without_a_gpu():
