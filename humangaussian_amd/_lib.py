@@ -14,7 +14,7 @@ import ctypes
 import os
 import shutil
 import subprocess
-from ctypes import POINTER, Structure, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_float, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_void_p
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
@@ -72,6 +72,21 @@ class HgsLbsArgs(Structure):
 
 LBS_MAX_JOINTS = 64
 LBS_FRAME_TILE = 8
+
+
+POSE_OPENPOSE, POSE_HUMANSD = 0, 1
+POSE_MAX_LIMBS, POSE_MAX_COLOURS, POSE_RECORD_INTS, POSE_MAX_DIM = 17, 18, 8, 4096
+
+
+class HgsPoseArgs(Structure):
+    """ctypes mirror of `hgs_pose_args` (hgs_pose_draw)."""
+    _fields_ = [
+        ("style", c_int32), ("B", c_int32), ("K", c_int32), ("H", c_int32), ("W", c_int32),
+        ("limb_width", c_int32), ("uint8_out", c_int32), ("num_limbs", c_int32),
+        ("points", c_void_p), ("mvp", c_void_p), ("occlusion", c_void_p), ("image", c_void_p), ("kp", c_void_p),
+        ("records", c_void_p),
+        ("limb", (c_int32 * 3) * POSE_MAX_LIMBS), ("colour", (c_uint8 * 3) * POSE_MAX_COLOURS),
+    ]
 
 
 class HgsStatus(Structure):
@@ -133,6 +148,8 @@ EXPORTS = {
     "hgs_adam_step": (ctypes.c_int, [POINTER(HgsAdamArgs), c_void_p]),
     "hgs_lbs_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "hgs_lbs_pose": (ctypes.c_int, [POINTER(HgsLbsArgs), c_void_p]),
+    "hgs_pose_records_bytes": (c_size_t, [c_int32, c_int32]),
+    "hgs_pose_draw": (ctypes.c_int, [POINTER(HgsPoseArgs), c_void_p]),
     "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

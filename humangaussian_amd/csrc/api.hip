@@ -9,6 +9,7 @@
 #include "hgs_common.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -27,6 +28,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "bookkeeping.hip"
 #include "optim.hip"
 #include "lbs.hip"
+#include "pose.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -988,6 +990,63 @@ int hgs_lbs_pose(const hgs_lbs_args* args, void* stream_) {
   HGS_LAUNCH_CHECK();
   if (one) hipLaunchKernelGGL(hgs_k_lbs_skin_f1, dim3((unsigned)blocks), dim3(HGS_LBS_THREADS), 0, stream, a);
   else hipLaunchKernelGGL(hgs_k_lbs_skin_f8, dim3((unsigned)blocks), dim3(HGS_LBS_THREADS), 0, stream, a);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+size_t hgs_pose_records_bytes(int32_t style, int32_t B) {
+  if ((style != HGS_POSE_OPENPOSE && style != HGS_POSE_HUMANSD) || B < 0) return 0;
+  return (size_t)B * hgs_pose_num_records(style) * HGS_POSE_RECORD_INTS * sizeof(int32_t);
+}
+
+namespace {
+// the styles' own tables, from their public definitions: {colour index, keypoint a, keypoint b}.
+// HumanSD: the COCO-17 skeleton in the order MMPose's HumanSD drawing lists it, colours int(255 c) of seaborn's
+// hls_palette(16) (hues i / 16 + 0.01 through colorsys.hls_to_rgb(h, .6, .65)).  OpenPose: the 17 limbs of the 18-point
+// body model, limb i in colour i of the controlnet_aux list.
+const int32_t POSE_LIMBS_HUMANSD[16][3] = {
+    {1, 0, 1}, {0, 0, 2}, {3, 1, 3}, {2, 2, 4}, {5, 3, 5}, {4, 4, 6}, {7, 5, 7}, {6, 6, 8},
+    {9, 7, 9}, {8, 8, 10}, {11, 5, 11}, {10, 6, 12}, {13, 11, 13}, {12, 12, 14}, {15, 13, 15}, {14, 14, 16}};
+const uint8_t POSE_COLOURS_HUMANSD[16][3] = {
+    {219, 94, 86}, {219, 144, 86}, {219, 194, 86}, {194, 219, 86}, {145, 219, 86}, {95, 219, 86}, {86, 219, 127}, {86, 219, 177},
+    {86, 211, 219}, {86, 161, 219}, {86, 111, 219}, {111, 86, 219}, {160, 86, 219}, {210, 86, 219}, {219, 86, 178}, {219, 86, 128}};
+const int32_t POSE_LIMBS_OPENPOSE[17][3] = {
+    {0, 0, 1}, {1, 1, 2}, {2, 2, 3}, {3, 3, 4}, {4, 1, 5}, {5, 5, 6}, {6, 6, 7}, {7, 1, 8}, {8, 8, 9},
+    {9, 9, 10}, {10, 1, 11}, {11, 11, 12}, {12, 12, 13}, {13, 0, 14}, {14, 14, 16}, {15, 0, 15}, {16, 15, 17}};
+const uint8_t POSE_COLOURS_OPENPOSE[18][3] = {
+    {255, 0, 0}, {255, 85, 0}, {255, 170, 0}, {255, 255, 0}, {170, 255, 0}, {85, 255, 0}, {0, 255, 0}, {0, 255, 85}, {0, 255, 170},
+    {0, 255, 255}, {0, 170, 255}, {0, 85, 255}, {0, 0, 255}, {85, 0, 255}, {170, 0, 255}, {255, 0, 255}, {255, 0, 170}, {255, 0, 85}};
+}  // namespace
+
+// One launch (pose.hip): a workgroup per (64 x 16 pixel tile, view).
+int hgs_pose_draw(const hgs_pose_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  hgs_pose_args a = *args;
+  if (a.style != HGS_POSE_OPENPOSE && a.style != HGS_POSE_HUMANSD) return HGS_EINVAL;
+  const bool humansd = a.style == HGS_POSE_HUMANSD;
+  if (a.K != (humansd ? 17 : 18)) return HGS_EINVAL;
+  if (a.B < 0 || a.B > 65535) return HGS_EINVAL;
+  if (a.H < 1 || a.H > HGS_POSE_MAX_DIM || a.W < 1 || a.W > HGS_POSE_MAX_DIM) return HGS_EINVAL;
+  if (a.limb_width < 1 || a.limb_width > 32767) return HGS_EINVAL;
+  const int max_limbs = humansd ? HGS_POSE_MAX_LIMBS - 1 : HGS_POSE_MAX_LIMBS;
+  if (a.num_limbs < 0 || a.num_limbs > max_limbs) return HGS_EINVAL;
+  if (a.num_limbs == 0) {
+    a.num_limbs = max_limbs;
+    memset(a.limb, 0, sizeof(a.limb));
+    memset(a.colour, 0, sizeof(a.colour));
+    if (humansd) { memcpy(a.limb, POSE_LIMBS_HUMANSD, sizeof(POSE_LIMBS_HUMANSD)); memcpy(a.colour, POSE_COLOURS_HUMANSD, sizeof(POSE_COLOURS_HUMANSD)); }
+    else { memcpy(a.limb, POSE_LIMBS_OPENPOSE, sizeof(POSE_LIMBS_OPENPOSE)); memcpy(a.colour, POSE_COLOURS_OPENPOSE, sizeof(POSE_COLOURS_OPENPOSE)); }
+  } else {
+    for (int i = 0; i < a.num_limbs; ++i)
+      if (a.limb[i][0] < 0 || a.limb[i][0] >= HGS_POSE_MAX_COLOURS || a.limb[i][1] < 0 || a.limb[i][1] >= a.K ||
+          a.limb[i][2] < 0 || a.limb[i][2] >= a.K)
+        return HGS_EINVAL;
+  }
+  if (a.B == 0) return HGS_OK;
+  if (!a.points || !a.mvp || !a.image || !a.kp || !a.records) return HGS_EINVAL;
+  const unsigned tiles = (unsigned)((a.W + HGS_POSE_TILE_W - 1) / HGS_POSE_TILE_W) * (unsigned)((a.H + HGS_POSE_TILE_H - 1) / HGS_POSE_TILE_H);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_pose_draw, dim3(tiles, (unsigned)a.B), dim3(HGS_POSE_THREADS), 0, stream, a);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -980,6 +980,49 @@ std::tuple<Tensor, c10::optional<Tensor>> lbs_pose(const Tensor& v_shaped, const
   return {vertices, return_joints ? c10::optional<Tensor>(joints) : c10::nullopt};
 }
 
+// ---- pose-control images (include/hgs_rast.h: hgs_pose_draw): B views of one skeleton in one launch on the current
+// stream, nothing read back.  points (K, 4) fp32, mvp (B, 4, 4) fp32, occlusion (B,) uint8 or None.  Returns (image
+// (B, H, W, 3) fp32 or uint8, kp (B, K, 3), records (B, R, 8) int32).
+std::tuple<Tensor, Tensor, Tensor> pose_draw(const Tensor& points, const Tensor& mvp, const c10::optional<Tensor>& occlusion,
+                                             int64_t style, int64_t H, int64_t W, int64_t limb_width, bool uint8_out) {
+  at::NoGradGuard ng;
+  const c10::Device dev = mvp.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(points, dev, at::kFloat, "pose_draw: points");
+  need_dev(mvp, dev, at::kFloat, "pose_draw: mvp");
+  if (style != HGS_POSE_OPENPOSE && style != HGS_POSE_HUMANSD) throw std::runtime_error("pose_draw: style is 0 (OpenPose) or 1 (HumanSD)");
+  const int64_t K = style == HGS_POSE_HUMANSD ? 17 : 18;
+  if (points.dim() != 2 || points.size(0) != K || points.size(1) != 4)
+    throw std::runtime_error("pose_draw: points must be (" + std::to_string(K) + ", 4) for this style");
+  if (mvp.dim() != 3 || mvp.size(1) != 4 || mvp.size(2) != 4) throw std::runtime_error("pose_draw: mvp must be (B, 4, 4)");
+  const int64_t B = mvp.size(0);
+  if (B > 65535) throw std::runtime_error("pose_draw: at most 65535 views");
+  if (H < 1 || H > HGS_POSE_MAX_DIM || W < 1 || W > HGS_POSE_MAX_DIM)
+    throw std::runtime_error("pose_draw: H and W must be in [1, " + std::to_string(HGS_POSE_MAX_DIM) + "]");
+  if (limb_width < 1 || limb_width > 32767) throw std::runtime_error("pose_draw: limb_width must be in [1, 32767], got " + std::to_string(limb_width));
+  hgs_pose_args a{};
+  a.style = (int32_t)style; a.B = (int32_t)B; a.K = (int32_t)K; a.H = (int32_t)H; a.W = (int32_t)W;
+  a.limb_width = (int32_t)limb_width;
+  a.uint8_out = uint8_out ? 1 : 0;
+  if (occlusion.has_value() && occlusion->defined()) {
+    need_dev(*occlusion, dev, at::kByte, "pose_draw: occlusion");
+    if (occlusion->numel() != B) throw std::runtime_error("pose_draw: occlusion must be (B,)");
+    a.occlusion = B > 0 ? occlusion->data_ptr<uint8_t>() : nullptr;
+  }
+  const int64_t R = (int64_t)(hgs_pose_records_bytes(a.style, 1) / (HGS_POSE_RECORD_INTS * sizeof(int32_t)));
+  Tensor image = at::empty({B, H, W, 3}, mvp.options().dtype(uint8_out ? at::kByte : at::kFloat));
+  Tensor kp = at::empty({B, K, 3}, mvp.options());
+  Tensor records = at::empty({B, R, HGS_POSE_RECORD_INTS}, mvp.options().dtype(at::kInt));
+  a.points = fptr(points);
+  a.mvp = fptr(mvp);
+  a.image = B > 0 ? image.data_ptr() : nullptr;
+  a.kp = fptr_mut(kp);
+  a.records = B > 0 ? records.data_ptr<int32_t>() : nullptr;
+  check_rc(hgs_pose_draw(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_pose_draw");
+  return {image, kp, records};
+}
+
 void set_stage_events(const c10::optional<std::vector<int64_t>>& fwd, const c10::optional<std::vector<int64_t>>& bwd) {
   g_stage_fwd.clear();
   g_stage_bwd.clear();
@@ -1210,6 +1253,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight_joint"), py::arg("weight_value"), py::arg("poses"), py::arg("transl") = py::none(),
         py::arg("centre") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("scale") = 1.0, py::arg("return_joints") = false,
         py::call_guard<py::gil_scoped_release>());
+  m.def("pose_draw", &pose_draw, py::arg("points"), py::arg("mvp"), py::arg("occlusion"), py::arg("style"), py::arg("H"),
+        py::arg("W"), py::arg("limb_width"), py::arg("uint8_out") = false, py::call_guard<py::gil_scoped_release>());
   m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());

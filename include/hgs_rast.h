@@ -459,6 +459,78 @@ typedef struct hgs_lbs_args {
 size_t hgs_lbs_workspace_bytes(int32_t J, int32_t F);
 int hgs_lbs_pose(const hgs_lbs_args* args, void* stream);
 
+/* ---- pose-control images: B views of one skeleton in one launch (the reference's Skeleton.draw / humansd_draw) ---------
+ * The reference's training step (threestudio/systems/GaussianDreamer.py:268-287) copies each view's mvp matrix to the
+ * host, draws a skeleton map with cv2 on the CPU (threestudio/utils/poser.py:361-459, :8-49) and uploads the float image.
+ * hgs_pose_draw draws all B views on the device.  This definition is the contract; it is NOT cv2 pixel for pixel (outline
+ * pixels may differ: cv2 fills a fixed-point polygon, a 360-gon for an ellipse and a midpoint circle).
+ * points [K][4] fp32 (homogeneous, already in the reference's swapped axes), mvp [B][4][4] fp32 row-major, occlusion [B]
+ * uint8 or NULL (no view occluded).  K = 17 for HGS_POSE_HUMANSD, 18 for HGS_POSE_OPENPOSE.  Outputs: image [B][H][W][3]
+ * (fp32 in [0, 1], or uint8 with uint8_out != 0), kp [B][K][3] fp32 (xs, ys, conf), records [B][R][8] int32 with
+ * R = hgs_pose_records_bytes(style, 1) / 32 (16 or 35).  Every byte of the three is written exactly once (no atomics:
+ * the caller may pass uninitialised storage and a call is bit-reproducible); view b has the bits of a call with it alone.
+ * Projection (poser.py:365-369, :420-424), fp32 with every operation rounded once, m = mvp[b], p = points[k]:
+ *   clip_c = fma(m[c][3], p3, fma(m[c][2], p2, fma(m[c][1], p1, m[c][0] * p0)));  ndc_c = clip_c / clip_3 (IEEE division);
+ *   xs = (ndc_0 + 1) / 2 * H,  ys = (ndc_1 + 1) / 2 * W - x with H and y with W, as the reference has it; the pixel COLUMN
+ *   is int(xs) and the ROW int(ys), truncated toward zero (cv2 points are (x = column, y = row)).
+ * Occlusion (:373-389, :428-445), for a view whose flag is set, with z = ndc_2, nose n = 0 and (left ear, right ear,
+ * left eye, right eye) = (el, er, yl, yr) = (3, 4, 1, 2) for HumanSD and (17, 16, 15, 14) for OpenPose:
+ *   z[n] > z[el] and z[n] < z[er]:  er is hidden, and yr too if xs[yr] > xs[yl];
+ *   else z[n] < z[el] and z[n] > z[er]:  el is hidden, and yl too if xs[yl] < xs[yr];
+ *   else z[n] > z[el] and z[n] > z[er]:  n, yl and yr are hidden;  else nothing is.
+ * A keypoint is UNUSABLE if xs or ys is not finite or exceeds 8191 in magnitude (w <= 0 puts a point far away); no limb
+ * that touches one is drawn (the reference would raise in int() or let cv2 clip).  With |coordinate| <= 8191, pixels in
+ * [0, 4096) and limb_width <= 32767: every difference is below 2^14, every dot and cross product of two below 2^29, so
+ * 4 cross^2 < 2^60 and w^2 L < 2^59 - the integer tests below cannot overflow int64.
+ * HGS_POSE_HUMANSD (draw_humansd_skeleton): conf = 1, or 0 for a hidden keypoint.  Limb (colour, a, b) of the table is
+ *   drawn iff conf[a] > 0.3, conf[b] > 0.3, both are usable and the view's sum over k (in order, fp32) of
+ *   (xs + ys) + conf is > 0 (np.sum(pose) > 0).  Record {1, Ax, Ay, Bx, By, w, 0, rgb}: the capsule around the segment
+ *   between the truncated integer endpoints A and B covers pixel P iff 4 d^2(P, AB) <= w^2, exactly: with t = AP.AB,
+ *   L = AB.AB:  t <= 0: 4 |AP|^2 <= w^2;  t >= L: 4 |BP|^2 <= w^2;  else 4 (AP x AB)^2 <= w^2 L.  (cv2.line of thickness w
+ *   plus the reference's end circles of radius w / 2, which lie inside the capsule.)  w = limb_width.
+ * HGS_POSE_OPENPOSE (Skeleton.draw): conf = mask = 0 <= xs < H and 0 <= ys < W and not hidden.  First a disc per
+ *   masked-in keypoint i, record {2, cx, cy, 16, 0, 0, 0, rgb(colour[i])}: dx^2 + dy^2 <= 16.  Then limb i of the table
+ *   iff both its keypoints are masked in, record {3, cx, cy, a, theta, 4, 0, rgb}: centre (int((X0 + X1) / 2),
+ *   int((Y0 + Y1) / 2)), a = int(sqrt((Y0 - Y1)^2 + (X0 - X1)^2) / 2), theta = int(atan2(Y0 - Y1, X0 - X1) * (180 / pi)),
+ *   all fp32.  With T[k] = lround(16384 cos(k degrees)) (csrc/pose_trig.h), C = T[theta mod 360], S = T[(theta - 90) mod
+ *   360], u = dx C + dy S, v = dy C - dx S and b = 4 the pixel at (dx, dy) from the centre is inside iff |u| <= a 2^14,
+ *   |v| <= b 2^14 and u^2 b^2 + v^2 a^2 <= a^2 b^2 2^28 (after the first two the third stays below 2^58; a = 0 leaves the
+ *   pixels with u = 0).
+ * A record of an element that is not drawn is all zeros.  The raster reads the records and nothing else: a pixel starts
+ * at 0 and takes the records in order; 1 and 2 overwrite it with rgb, 3 blends every channel as cv2.addWeighted(canvas,
+ * .4, cur, .6, 0) does on uint8, c <- (4 c + 6 k + 5) / 10 in integers (the exact (2 c + 3 k) / 5 is never on a tie).
+ * rgb = r | g << 8 | b << 16.  Output: float32(v) / float32(255) correctly rounded, or v itself for uint8.
+ * Tables: num_limbs = 0 takes the style's own (HumanSD: the reference's 16 limbs and int(255 c) of seaborn's 16-colour hls
+ * palette; OpenPose: its 17 limbs and the controlnet_aux colours); else limb[i] = {colour index, a, b} for i < num_limbs <=
+ * HGS_POSE_MAX_LIMBS with indices inside the style's K and HGS_POSE_MAX_COLOURS, colour[i] = {r, g, b}.
+ * Returns HGS_EINVAL without a launch for args == NULL, a style other than the two, a K that does not fit the style,
+ * B < 0 or > 65535, H or W outside [1, 4096], limb_width outside [1, 32767], a table out of range, or a NULL points / mvp /
+ * image / kp / records with B > 0; B == 0: HGS_OK without a launch.
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_POSE_OPENPOSE 0
+#define HGS_POSE_HUMANSD 1
+#define HGS_POSE_MAX_LIMBS 17
+#define HGS_POSE_MAX_COLOURS 18
+#define HGS_POSE_RECORD_INTS 8
+#define HGS_POSE_MAX_DIM 4096
+typedef struct hgs_pose_args {
+  int32_t style;                 /* HGS_POSE_OPENPOSE or HGS_POSE_HUMANSD */
+  int32_t B, K, H, W;
+  int32_t limb_width;            /* HumanSD: the capsule's width w (the reference: int(10 H / 512)); OpenPose: >= 1, unused */
+  int32_t uint8_out;             /* image is uint8 instead of fp32 */
+  int32_t num_limbs;             /* 0: the style's own tables */
+  const float* points;
+  const float* mvp;
+  const uint8_t* occlusion;      /* or NULL */
+  void* image;
+  float* kp;
+  int32_t* records;
+  int32_t limb[HGS_POSE_MAX_LIMBS][3];
+  uint8_t colour[HGS_POSE_MAX_COLOURS][3];
+} hgs_pose_args;
+size_t hgs_pose_records_bytes(int32_t style, int32_t B);   /* 0 for an unknown style or B < 0 */
+int hgs_pose_draw(const hgs_pose_args* args, void* stream);
+
 /* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
  * The per-avatar anchoring of /root/reference/animation.py:333-378:
  *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
