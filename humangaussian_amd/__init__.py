@@ -6,6 +6,7 @@ Only what the rasterize hot path needs:
   rasterizer.py    GaussianRasterizationSettings / GaussianRasterizer (reference API mirror)
   renderer.py      render() / Renderer.render() mirrors (the reference's two call sites)
   view_parallel.py view-parallel multi-GPU rendering (one RCCL all-gather per step)
+  step_images.py   guidance_images(): the guidance's two images and the opacity losses of a step
   synth.py         synthetic SMPL-X-like clouds + threestudio-style cameras (bench/tests)
 """
 from .rasterizer import (  # noqa: F401
@@ -15,5 +16,7 @@ from .rasterizer import (  # noqa: F401
     rasterize_gaussians_batch,
 )
 
+from .step_images import StepImages, guidance_images  # noqa: F401
+
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
-           "rasterize_gaussians_batch"]
+           "rasterize_gaussians_batch", "StepImages", "guidance_images"]

@@ -89,6 +89,21 @@ class HgsPoseArgs(Structure):
     ]
 
 
+SI_PIXELS_PER_THREAD, SI_PIXELS_PER_WORKGROUP, SI_PARTIALS_PER_VIEW, SI_MAX_DIM = 4, 1024, 256, 32768
+
+
+class HgsStepImagesArgs(Structure):
+    """ctypes mirror of `hgs_step_images_args` (hgs_step_images_forward / _backward)."""
+    _fields_ = [
+        ("B", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32), ("half_images", c_int32),
+        ("render", c_void_p), ("depth", c_void_p), ("workspace", c_void_p), ("rgb_out", c_void_p), ("depth_out", c_void_p),
+        ("loss_sparsity", c_void_p), ("loss_opaque", c_void_p), ("depth_min", c_void_p), ("depth_max", c_void_p),
+        ("depth_global_max", c_void_p), ("tie_counts", c_void_p),
+        ("grad_rgb", c_void_p), ("grad_depth", c_void_p), ("grad_loss_sparsity", c_void_p), ("grad_loss_opaque", c_void_p),
+        ("grad_render", c_void_p), ("grad_depth_in", c_void_p),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -150,6 +165,9 @@ EXPORTS = {
     "hgs_lbs_pose": (ctypes.c_int, [POINTER(HgsLbsArgs), c_void_p]),
     "hgs_pose_records_bytes": (c_size_t, [c_int32, c_int32]),
     "hgs_pose_draw": (ctypes.c_int, [POINTER(HgsPoseArgs), c_void_p]),
+    "hgs_step_images_workspace_bytes": (c_size_t, [c_int32] * 5),
+    "hgs_step_images_forward": (ctypes.c_int, [POINTER(HgsStepImagesArgs), c_void_p]),
+    "hgs_step_images_backward": (ctypes.c_int, [POINTER(HgsStepImagesArgs), c_void_p]),
     "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

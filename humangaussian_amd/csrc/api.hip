@@ -29,6 +29,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "optim.hip"
 #include "lbs.hip"
 #include "pose.hip"
+#include "step_images.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -1047,6 +1048,79 @@ int hgs_pose_draw(const hgs_pose_args* args, void* stream_) {
   const unsigned tiles = (unsigned)((a.W + HGS_POSE_TILE_W - 1) / HGS_POSE_TILE_W) * (unsigned)((a.H + HGS_POSE_TILE_H - 1) / HGS_POSE_TILE_H);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_pose_draw, dim3(tiles, (unsigned)a.B), dim3(HGS_POSE_THREADS), 0, stream, a);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+namespace {
+// sizes both entry points and the workspace rule accept
+bool step_images_sizes_ok(int32_t B, int32_t H, int32_t W, int32_t h, int32_t w) {
+  if (B < 1 || H < 1 || W < 1 || h < 1 || w < 1 || h > H || w > W) return false;
+  if (H > HGS_SI_MAX_DIM || W > HGS_SI_MAX_DIM) return false;
+  return (long long)B * H * W <= 0x7fffffffll;
+}
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+}  // namespace
+
+size_t hgs_step_images_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t h, int32_t w) {
+  if (!step_images_sizes_ok(B, H, W, h, w)) return 0;
+  const size_t n = (size_t)B * hgs_si_partials(H, W);
+  const size_t fwd = HGS_SI_WS_FWD_WORDS * n, bwd = HGS_SI_WS_BWD_WORDS * n + 2 * (size_t)B + 1;
+  return hgs_align_up(std::max(fwd, bwd) * 4, 256);
+}
+
+// Three launches (step_images.hip): depth min / max partials; loss partials beside the image planes; one workgroup that
+// combines the partials in a fixed order.
+int hgs_step_images_forward(const hgs_step_images_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_step_images_args& a = *args;
+  if (!step_images_sizes_ok(a.B, a.H, a.W, a.h, a.w)) return HGS_EINVAL;
+  if (!a.render || !a.depth || !a.workspace || !a.rgb_out || !a.depth_out || !a.loss_sparsity || !a.loss_opaque ||
+      !a.depth_min || !a.depth_max || !a.depth_global_max || !a.tie_counts)
+    return HGS_EINVAL;
+  if (!aligned16(a.render) || !aligned16(a.depth) || !aligned16(a.workspace) || !aligned16(a.rgb_out) || !aligned16(a.depth_out))
+    return HGS_EINVAL;
+  const int P = hgs_si_partials(a.H, a.W);
+  const long long per_plane = ((long long)a.h * ((a.w + 3) / 4) + HGS_SI_THREADS - 1) / HGS_SI_THREADS;
+  const long long blocks = (long long)a.B * P + 4ll * a.B * per_plane;
+  if (blocks > 0x7fffffffll || a.B > 65535) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_si_minmax, dim3((unsigned)P, (unsigned)a.B), dim3(HGS_SI_THREADS), 0, stream, a);
+  HGS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hgs_k_si_forward, dim3((unsigned)blocks), dim3(HGS_SI_THREADS), 0, stream, a, P, (int)per_plane);
+  HGS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hgs_k_si_finish, dim3(1), dim3(HGS_SI_THREADS), 0, stream, a, P);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+// Three launches: partials of the three tie-share sums; one workgroup that turns them into shares; the two gradients.
+// With grad_rgb alone the first two are skipped.
+int hgs_step_images_backward(const hgs_step_images_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_step_images_args& a = *args;
+  if (!step_images_sizes_ok(a.B, a.H, a.W, a.h, a.w)) return HGS_EINVAL;
+  const bool want_depth = a.grad_depth || a.grad_loss_sparsity || a.grad_loss_opaque;
+  if (!a.grad_rgb && !want_depth) return HGS_OK;
+  if (a.grad_rgb && (!a.grad_render || !aligned16(a.grad_rgb) || !aligned16(a.grad_render))) return HGS_EINVAL;
+  if (want_depth) {
+    if (!a.depth || !a.workspace || !a.depth_min || !a.depth_max || !a.depth_global_max || !a.tie_counts || !a.grad_depth_in)
+      return HGS_EINVAL;
+    if (!aligned16(a.depth) || !aligned16(a.workspace) || !aligned16(a.grad_depth_in) || !aligned16(a.grad_depth)) return HGS_EINVAL;
+  }
+  const int P = hgs_si_partials(a.H, a.W);
+  const int planes = (a.grad_rgb ? 3 : 0) + (want_depth ? 1 : 0);
+  const long long per_plane = ((long long)a.H * ((a.W + 3) / 4) + HGS_SI_THREADS - 1) / HGS_SI_THREADS;
+  const long long blocks = (long long)planes * a.B * per_plane;
+  if (blocks > 0x7fffffffll || a.B > 65535) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (want_depth) {
+    hipLaunchKernelGGL(hgs_k_si_bwd_sums, dim3((unsigned)P, (unsigned)a.B), dim3(HGS_SI_THREADS), 0, stream, a);
+    HGS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hgs_k_si_bwd_finish, dim3(1), dim3(HGS_SI_THREADS), 0, stream, a, P);
+    HGS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(hgs_k_si_bwd_write, dim3((unsigned)blocks), dim3(HGS_SI_THREADS), 0, stream, a, P, (int)per_plane, planes);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -1023,6 +1023,116 @@ std::tuple<Tensor, Tensor, Tensor> pose_draw(const Tensor& points, const Tensor&
   return {image, kp, records};
 }
 
+// ---- the step's guidance images and opacity losses (include/hgs_rast.h: hgs_step_images_*): three launches each way on
+// the current stream, the workspace from the caching allocator, nothing read back.  render (B, 3, H, W) and depth
+// (B, 1, H, W) fp32 contiguous.  Forward returns (rgb, depth3 (B, 3, h, w) fp32 or fp16, loss_sparsity, loss_opaque (0-dim),
+// depth_min, depth_max (B,), depth_global_max (0-dim), tie_counts (2 B + 1,) int32).
+namespace {
+const void* si_aligned(Tensor& t) {   // the kernels take 16-byte accesses: a view into the middle of a storage is copied
+  if (((uintptr_t)t.data_ptr() & 15) != 0) t = t.clone();
+  return t.data_ptr();
+}
+hgs_step_images_args si_args(const Tensor& depth, int64_t h, int64_t w, bool half_images, const char* who) {
+  if (depth.dim() != 4 || depth.size(1) != 1) throw std::runtime_error(std::string(who) + ": depth must be (B, 1, H, W)");
+  const int64_t B = depth.size(0), H = depth.size(2), W = depth.size(3);
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || H > HGS_SI_MAX_DIM || W > HGS_SI_MAX_DIM || B * H * W > 0x7fffffffll)
+    throw std::runtime_error(std::string(who) + ": 1..65535 views of at most " + std::to_string(HGS_SI_MAX_DIM) + " pixels a side, fewer than 2^31 pixels in all");
+  if (h < 1 || w < 1 || h > H || w > W) throw std::runtime_error(std::string(who) + ": the output size must be within [1, H] x [1, W] (no upsampling)");
+  hgs_step_images_args a{};
+  a.B = (int32_t)B; a.H = (int32_t)H; a.W = (int32_t)W; a.h = (int32_t)h; a.w = (int32_t)w;
+  a.half_images = half_images ? 1 : 0;
+  return a;
+}
+Tensor si_workspace(const hgs_step_images_args& a, const c10::Device& dev) {
+  return at::empty({(int64_t)hgs_step_images_workspace_bytes(a.B, a.H, a.W, a.h, a.w)}, at::TensorOptions().dtype(at::kByte).device(dev));
+}
+}  // namespace
+
+std::vector<Tensor> step_images_forward(Tensor render, Tensor depth, int64_t h, int64_t w, bool half_images) {
+  at::NoGradGuard ng;
+  const c10::Device dev = depth.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(render, dev, at::kFloat, "step_images_forward: render");
+  need_dev(depth, dev, at::kFloat, "step_images_forward: depth");
+  hgs_step_images_args a = si_args(depth, h, w, half_images, "step_images_forward");
+  if (render.dim() != 4 || render.size(0) != a.B || render.size(1) != 3 || render.size(2) != a.H || render.size(3) != a.W)
+    throw std::runtime_error("step_images_forward: render must be (B, 3, H, W) with depth's B, H, W");
+  const auto fopt = depth.options();
+  const auto iopt = fopt.dtype(half_images ? at::kHalf : at::kFloat);
+  Tensor rgb = at::empty({a.B, 3, h, w}, iopt), depth3 = at::empty({a.B, 3, h, w}, iopt);
+  Tensor ls = at::empty({}, fopt), lo = at::empty({}, fopt), gmax = at::empty({}, fopt), dmin = at::empty({a.B}, fopt), dmax = at::empty({a.B}, fopt);
+  Tensor counts = at::empty({2 * (int64_t)a.B + 1}, fopt.dtype(at::kInt));
+  Tensor work = si_workspace(a, dev);
+  a.render = static_cast<const float*>(si_aligned(render));
+  a.depth = static_cast<const float*>(si_aligned(depth));
+  a.workspace = work.data_ptr();
+  a.rgb_out = rgb.data_ptr();
+  a.depth_out = depth3.data_ptr();
+  a.loss_sparsity = ls.data_ptr<float>();
+  a.loss_opaque = lo.data_ptr<float>();
+  a.depth_global_max = gmax.data_ptr<float>();
+  a.depth_min = dmin.data_ptr<float>();
+  a.depth_max = dmax.data_ptr<float>();
+  a.tie_counts = reinterpret_cast<uint32_t*>(counts.data_ptr<int32_t>());
+  check_rc(hgs_step_images_forward(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_step_images_forward");
+  return {rgb, depth3, ls, lo, dmin, dmax, gmax, counts};
+}
+
+// The gradient of the above.  depth and the forward's depth_min / depth_max / depth_global_max / tie_counts; the four
+// incoming gradients, each optional (None: absent).  Returns (grad_render or None, grad_depth or None).
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>> step_images_backward(
+    Tensor depth, const Tensor& dmin, const Tensor& dmax, const Tensor& gmax, const Tensor& counts, int64_t h, int64_t w,
+    bool half_images, c10::optional<Tensor> grad_rgb, c10::optional<Tensor> grad_depth, c10::optional<Tensor> grad_ls,
+    c10::optional<Tensor> grad_lo) {
+  at::NoGradGuard ng;
+  const c10::Device dev = depth.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(depth, dev, at::kFloat, "step_images_backward: depth");
+  need_dev(dmin, dev, at::kFloat, "step_images_backward: depth_min");
+  need_dev(dmax, dev, at::kFloat, "step_images_backward: depth_max");
+  need_dev(gmax, dev, at::kFloat, "step_images_backward: depth_global_max");
+  need_dev(counts, dev, at::kInt, "step_images_backward: tie_counts");
+  hgs_step_images_args a = si_args(depth, h, w, half_images, "step_images_backward");
+  if (dmin.numel() != a.B || dmax.numel() != a.B || gmax.numel() != 1 || counts.numel() != 2 * (int64_t)a.B + 1)
+    throw std::runtime_error("step_images_backward: depth_min / depth_max (B,), depth_global_max (1), tie_counts (2 B + 1,)");
+  const at::ScalarType ity = half_images ? at::kHalf : at::kFloat;
+  auto image_grad = [&](c10::optional<Tensor>& g, const char* name) -> const void* {
+    if (!g.has_value() || !g->defined()) return nullptr;
+    need_dev(*g, dev, ity, name);
+    if (g->numel() != (int64_t)a.B * 3 * h * w) throw std::runtime_error(std::string(name) + " must be (B, 3, h, w)");
+    return si_aligned(*g);
+  };
+  auto scalar_grad = [&](c10::optional<Tensor>& g, const char* name) -> const float* {
+    if (!g.has_value() || !g->defined()) return nullptr;
+    need_dev(*g, dev, at::kFloat, name);
+    if (g->numel() != 1) throw std::runtime_error(std::string(name) + " must have one element");
+    return g->data_ptr<float>();
+  };
+  a.grad_rgb = image_grad(grad_rgb, "step_images_backward: grad_rgb");
+  a.grad_depth = image_grad(grad_depth, "step_images_backward: grad_depth");
+  a.grad_loss_sparsity = scalar_grad(grad_ls, "step_images_backward: grad_loss_sparsity");
+  a.grad_loss_opaque = scalar_grad(grad_lo, "step_images_backward: grad_loss_opaque");
+  const bool want_depth = a.grad_depth || a.grad_loss_sparsity || a.grad_loss_opaque;
+  Tensor d_render, d_depth, work;
+  if (a.grad_rgb) d_render = at::empty({a.B, 3, a.H, a.W}, depth.options());
+  if (want_depth) {
+    d_depth = at::empty({a.B, 1, a.H, a.W}, depth.options());
+    work = si_workspace(a, dev);
+    a.workspace = work.data_ptr();
+  }
+  a.depth = static_cast<const float*>(si_aligned(depth));
+  a.depth_min = const_cast<float*>(dmin.data_ptr<float>());
+  a.depth_max = const_cast<float*>(dmax.data_ptr<float>());
+  a.depth_global_max = const_cast<float*>(gmax.data_ptr<float>());
+  a.tie_counts = reinterpret_cast<uint32_t*>(const_cast<int32_t*>(counts.data_ptr<int32_t>()));
+  a.grad_render = a.grad_rgb ? d_render.data_ptr<float>() : nullptr;
+  a.grad_depth_in = want_depth ? d_depth.data_ptr<float>() : nullptr;
+  check_rc(hgs_step_images_backward(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_step_images_backward");
+  return {a.grad_rgb ? c10::optional<Tensor>(d_render) : c10::nullopt, want_depth ? c10::optional<Tensor>(d_depth) : c10::nullopt};
+}
+
 void set_stage_events(const c10::optional<std::vector<int64_t>>& fwd, const c10::optional<std::vector<int64_t>>& bwd) {
   g_stage_fwd.clear();
   g_stage_bwd.clear();
@@ -1255,6 +1365,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("pose_draw", &pose_draw, py::arg("points"), py::arg("mvp"), py::arg("occlusion"), py::arg("style"), py::arg("H"),
         py::arg("W"), py::arg("limb_width"), py::arg("uint8_out") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("step_images_forward", &step_images_forward, py::arg("render"), py::arg("depth"), py::arg("h"), py::arg("w"),
+        py::arg("half_images") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("step_images_backward", &step_images_backward, py::arg("depth"), py::arg("depth_min"), py::arg("depth_max"),
+        py::arg("depth_global_max"), py::arg("tie_counts"), py::arg("h"), py::arg("w"), py::arg("half_images"),
+        py::arg("grad_rgb") = py::none(), py::arg("grad_depth") = py::none(), py::arg("grad_loss_sparsity") = py::none(),
+        py::arg("grad_loss_opaque") = py::none(), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());

@@ -531,6 +531,81 @@ typedef struct hgs_pose_args {
 size_t hgs_pose_records_bytes(int32_t style, int32_t B);   /* 0 for an unknown style or B < 0 */
 int hgs_pose_draw(const hgs_pose_args* args, void* stream);
 
+/* ---- the step's guidance images and opacity losses (between render_views and the diffusion guidance) -------------------
+ * The reference stacks the B views' colour and depth (threestudio/systems/GaussianDreamer.py:285-302), normalises the
+ * depth per view and repeats it to three channels (:330-333), resizes both with F.interpolate(mode="bilinear",
+ * align_corners=False) and casts them (threestudio/models/guidance/dual_branch_guidance.py:762-770), and adds two losses
+ * on the depth (GaussianDreamer.py:359-366).  hgs_step_images_forward computes all of it in three launches,
+ * hgs_step_images_backward its gradient with respect to render and depth in three more; nothing is read back.
+ * Inputs: render [B][3][H][W] and depth [B][1][H][W], fp32, contiguous.  Both must be FINITE: a NaN or an Inf in either is
+ * outside this contract (min / max and the tie masks below are not defined for them).  Output size (h, w) with
+ * 1 <= h <= H and 1 <= w <= W: the same size or downsampling; upsampling is refused.
+ * Definition, every operation in fp32 rounded once unless said otherwise:
+ *   dmin[b], dmax[b] = min / max of depth[b] (:331-332, amin / amax);  g = max of depth over all views (:302, depths.max()).
+ *   nd      = (depth - dmin[b]) / (dmax[b] - dmin[b] + 1e-10f)                                   (:333)
+ *   rgb_out[b][c]        = resize(render[b][c]);   depth_out[b][0], [1], [2] = resize(nd[b]), the same bits three times:
+ *                          two contiguous [B][3][h][w] images, what the VAE is handed.
+ *   resize (torch's align_corners=False rule), per axis with in = H or W, out = h or w and scale = float(in) / float(out):
+ *     src = scale * (dst + 0.5f) - 0.5f, raised to 0 if negative;  i0 = min(int(src), in - 1);  i1 = min(i0 + 1, in - 1);
+ *     l = src - i0 clamped to [0, 1];  out = (1 - ly) ((1 - lx) v[y0][x0] + lx v[y0][x1]) + ly ((1 - lx) v[y1][x0] + lx v[y1][x1]).
+ *     At 2:1 l = 0.5 everywhere and this is the 2 x 2 box mean; at 16:1 (rgb_as_latents, 1024 -> 64) only 2 x 2 of every
+ *     16 x 16 inputs are read, as torch does.
+ *   op = depth / (g + 1e-5f)                                                                     (:302)
+ *   loss_sparsity = mean over B H W of sqrt(op^2 + 0.01f)                                        (:359-361)
+ *   loss_opaque   = mean of (x - 1) log(1 - x) - x log(x),  x = min(max(op, 1e-3f), 1 - 1e-3f)   (:363-366: binary_cross_entropy
+ *                   of the clamped opacity with ITSELF as the target)
+ *   half_images != 0: the two images are fp16, the fp32 result rounded once to nearest-even.
+ * The sums: every workgroup adds its pixels in a fixed order in fp32 and leaves one partial; one workgroup adds the
+ * partials in a fixed order in fp64.  No floating-point atomics anywhere: forward and backward are bit-reproducible.
+ * Backward: torch's autograd of the formulas above, for incoming gradients grad_rgb, grad_depth ([B][3][h][w], fp32 or
+ * fp16 as half_images says) and grad_loss_sparsity, grad_loss_opaque (one fp32 each, DEVICE memory, read by the kernel).
+ * A NULL gradient is absent (not a zero tensor).  In particular:
+ *   - dmin, dmax and g carry gradient: every element equal to the extremum receives grad / count (amin, amax and max()
+ *     all share evenly among ties; the counts are exact integers, written to tie_counts by the forward:
+ *     [b] = #(depth[b] == dmin[b]), [B + b] = #(depth[b] == dmax[b]), [2 B] = #(depth == g));
+ *   - binary_cross_entropy(x, x): the input's own gradient is 0 (as torch has it, (x - t) / (x (1 - x)) with t = x), the
+ *     target's is (log(1 - x) - log x) / N, and it passes the clamp only where 1e-3f <= op <= 1 - 1e-3f;
+ *   - an empty view (depth[b] all 0): dmax = dmin, the denominator is 1e-10f, nd = 0 exactly; the gradient through nd is
+ *     scaled by 1e10 - large, finite, and what torch computes.
+ * grad_render is written iff grad_rgb is given, grad_depth_in iff any of the other three is; every element once.
+ * The forward's depth_min, depth_max, depth_global_max and tie_counts are inputs of the backward.
+ * workspace: hgs_step_images_workspace_bytes(B, H, W, h, w) bytes, 16-byte aligned, scratch of ONE call (nothing in it
+ * lives from the forward to the backward).  render, depth, the images and the gradients must be 16-byte aligned.
+ * Both return HGS_EINVAL before any device work for args == NULL, B < 1 or > 65535, any size below 1, h > H, w > W, H or W
+ * above HGS_SI_MAX_DIM, B H W >= 2^31, a NULL or misaligned pointer among those the call needs; the backward with all four
+ * gradients NULL: HGS_OK without a launch.  hgs_step_images_workspace_bytes is 0 for sizes the calls refuse.
+ * The reductions cut a view into chunks of HGS_SI_PIXELS_PER_WORKGROUP pixels (HGS_SI_PIXELS_PER_THREAD per lane, one
+ * 16-byte load) and give it min(chunks, HGS_SI_PARTIALS_PER_VIEW) workgroups = partials.
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_SI_PIXELS_PER_THREAD 4
+#define HGS_SI_PIXELS_PER_WORKGROUP 1024
+#define HGS_SI_PARTIALS_PER_VIEW 256
+#define HGS_SI_MAX_DIM 32768
+typedef struct hgs_step_images_args {
+  int32_t B, H, W, h, w;
+  int32_t half_images;              /* rgb_out, depth_out, grad_rgb and grad_depth are fp16 instead of fp32 */
+  const float* render;              /* [B][3][H][W] (forward) */
+  const float* depth;               /* [B][1][H][W] */
+  void* workspace;
+  void* rgb_out;                    /* [B][3][h][w] (forward, written) */
+  void* depth_out;                  /* [B][3][h][w] (forward, written) */
+  float* loss_sparsity;             /* [1] (forward, written) */
+  float* loss_opaque;               /* [1] (forward, written) */
+  float* depth_min;                 /* [B] written by the forward, read by the backward */
+  float* depth_max;                 /* [B] likewise */
+  float* depth_global_max;          /* [1] likewise */
+  uint32_t* tie_counts;             /* [2 B + 1] likewise */
+  const void* grad_rgb;             /* [B][3][h][w] or NULL (backward) */
+  const void* grad_depth;           /* [B][3][h][w] or NULL */
+  const float* grad_loss_sparsity;  /* [1] on the device, or NULL */
+  const float* grad_loss_opaque;    /* [1] on the device, or NULL */
+  float* grad_render;               /* [B][3][H][W], written iff grad_rgb */
+  float* grad_depth_in;             /* [B][1][H][W], written iff any of the other three gradients is given */
+} hgs_step_images_args;
+size_t hgs_step_images_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t h, int32_t w);
+int hgs_step_images_forward(const hgs_step_images_args* args, void* stream);
+int hgs_step_images_backward(const hgs_step_images_args* args, void* stream);
+
 /* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
  * The per-avatar anchoring of /root/reference/animation.py:333-378:
  *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
