@@ -160,6 +160,7 @@ EXPORTS = {
     "hgs_compact_index": (ctypes.c_int, [c_int32] + [c_void_p] * 5),
     "hgs_gather_rows": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 4),
     "hgs_reanchor": (ctypes.c_int, [c_int32] + [c_void_p] * 7),
+    "hgs_reanchor_rot": (ctypes.c_int, [c_int32] + [c_void_p] * 6 + [c_int32] + [c_void_p] * 3),
     "hgs_adam_step": (ctypes.c_int, [POINTER(HgsAdamArgs), c_void_p]),
     "hgs_lbs_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "hgs_lbs_pose": (ctypes.c_int, [POINTER(HgsLbsArgs), c_void_p]),

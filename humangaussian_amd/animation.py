@@ -10,6 +10,9 @@ Reference: /root/reference/animation.py
              frame i belongs to rank i mod G (frames are independent units: no data-path collective is NEEDED; the
              optional image all-gather, one per round of G frames, runs under the render of the next round)
 
+Beyond the reference, opt-in and off by default: `AvatarAnimator(..., repose_rotations=True)` also carries every Gaussian's
+rotation with its anchor face (`MeshAnchoredGaussians.bind_rotations` / `positions_and_rotations`: hgs_reanchor_rot).
+
 The host logic (`render_frames_parallel`) takes the per-frame render as a callable, so it is testable on CPU with gloo; the
 product pieces (`MeshAnchoredGaussians`, `AvatarAnimator`) run on the HIP rasterizer only - there is no CPU fallback.
 """
@@ -29,7 +32,14 @@ from .view_parallel import _Gather, shard_views
 
 class MeshAnchoredGaussians:
     """Holds the static mapping (face index, barycentric uvw, signed distance along the face normal:
-    animation.py:339-345) on the device; `positions(vertices)` -> (P,3) for a posed mesh."""
+    animation.py:339-345) on the device; `positions(vertices)` -> (P,3) for a posed mesh.
+
+    Opt-in, beyond the reference (which moves positions only): `bind_rotations(rest_vertices, rotation_raw)` once, then
+    `positions_and_rotations(vertices)` -> ((P,3), (P,4)): every Gaussian's quaternion is carried by the rotation of its
+    anchor face from the rest mesh to the posed mesh, in the pass that writes its position (include/hgs_rast.h:
+    hgs_reanchor_rot; the face frame is e1 = first edge, n = face normal, e2 = n x e1).  The rotations returned are RAW
+    (they keep the length of `rotation_raw`; `get_rotation` normalises as always).  Scales are not re-posed and colours do
+    not rotate: with an active SH degree > 0 the view-dependent part stays in world axes."""
 
     def __init__(self, faces, mapping_face, mapping_uvw, mapping_dist, device="cuda"):
         dev = torch.device(device)
@@ -37,10 +47,32 @@ class MeshAnchoredGaussians:
         self.mapping_face = torch.as_tensor(mapping_face).to(dev, torch.int32).contiguous()
         self.mapping_uvw = torch.as_tensor(mapping_uvw).to(dev, torch.float32).contiguous()
         self.mapping_dist = torch.as_tensor(mapping_dist).to(dev, torch.float32).contiguous()
+        self.rot_base = None
 
     def positions(self, vertices) -> torch.Tensor:
         v = torch.as_tensor(vertices).to(self.faces.device, torch.float32).contiguous()
         return _lib.load_binding().reanchor(v, self.faces, self.mapping_face, self.mapping_uvw, self.mapping_dist)
+
+    def bind_rotations(self, rest_vertices, rotation_raw) -> torch.Tensor:
+        """rot_base[i] = conj(r(rest face of i)) (x) rotation_raw[i], kept on the device (one launch, once per avatar).
+        `rotation_raw`: (P,4) raw `_rotation` parameter, rows in the order of the mapping."""
+        v = torch.as_tensor(rest_vertices).to(self.faces.device, torch.float32).contiguous()
+        q = torch.as_tensor(rotation_raw).detach().to(self.faces.device, torch.float32).contiguous()
+        if q.dim() != 2 or q.shape[1] != 4 or q.shape[0] != self.mapping_face.numel():
+            raise ValueError(f"bind_rotations: rotation_raw must be ({self.mapping_face.numel()}, 4), got {tuple(q.shape)}")
+        self.rot_base = _lib.load_binding().reanchor_rot(v, self.faces, self.mapping_face, self.mapping_uvw,
+                                                         self.mapping_dist, q, True)[1]
+        return self.rot_base
+
+    def positions_and_rotations(self, vertices) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (xyz (P,3) with the bits of `positions(vertices)`, rot (P,4) = r(posed face of i) (x) rot_base[i]), one launch"""
+        if self.rot_base is None:
+            raise RuntimeError("MeshAnchoredGaussians.positions_and_rotations: call bind_rotations(rest_vertices, "
+                               "rotation_raw) first - there is no rest-pose frame to carry the rotations from")
+        v = torch.as_tensor(vertices).to(self.faces.device, torch.float32).contiguous()
+        xyz, rot = _lib.load_binding().reanchor_rot(v, self.faces, self.mapping_face, self.mapping_uvw, self.mapping_dist,
+                                                    self.rot_base, False)
+        return xyz, rot
 
 
 # ------------------------------------------------------------------------------ the motion that drives the frames
@@ -236,30 +268,50 @@ class AvatarAnimator:
     unless the caller moves it.  `gaussians` is any object with the reference GaussianModel getters and a writable
     `_xyz` (animation.py:403 assigns `self.gs.gaussians._xyz`).  antialiasing=True renders every frame with the
     rasterizer's screen-space antialiasing filter (`Renderer.render(..., antialiasing=True)`): thin structures keep
-    their coverage at resolutions and distances other than the training ones."""
+    their coverage at resolutions and distances other than the training ones.
+
+    repose_rotations=True (off by default; beyond the reference, which moves positions only and leaves every Gaussian's
+    orientation that of the rest pose): the animator binds `gaussians._rotation` to the anchor faces of `rest_vertices`
+    at construction (`MeshAnchoredGaussians.bind_rotations`), and `render_frame` then assigns `_xyz` AND `_rotation`, the
+    quaternion of each Gaussian carried by the rotation of its anchor face from the rest mesh to the posed one - flat or
+    elongated Gaussians stay in the surface when a limb swings.  What is NOT re-posed: scales; and colours do not rotate -
+    with an active SH degree > 0 the view-dependent part stays in world axes (the reference's animation always renders
+    with degree 0, animation.py:212, where there is nothing to rotate).  With the switch off `render_frame` is the
+    reference's path, call for call, and `_rotation` is never touched."""
 
     def __init__(self, gaussians, anchors: MeshAnchoredGaussians, white_background: bool = True, device="cuda",
-                 antialiasing: bool = False):
+                 antialiasing: bool = False, repose_rotations: bool = False, rest_vertices=None):
         from .renderer import Renderer
         self.gaussians, self.anchors = gaussians, anchors
         self.renderer = Renderer(gaussians, white_background=white_background, device=device)
         self.antialiasing = bool(antialiasing)
+        self.repose_rotations = bool(repose_rotations)
+        if self.repose_rotations:
+            if rest_vertices is None:
+                raise ValueError("AvatarAnimator(repose_rotations=True) needs rest_vertices=: the mesh the avatar was anchored on")
+            anchors.bind_rotations(rest_vertices, gaussians._rotation)
 
     @classmethod
     def from_rest_pose(cls, gaussians, vertices, faces, max_error: float = 0.01, **kw) -> "AvatarAnimator":
         """The animator of a trained avatar: `anchor_to_mesh(gaussians.get_xyz, vertices, faces, max_error)` on its rest-pose
         body mesh, then the culling of the reference (animation.py:365-371): the six tensors `_xyz`, `_features_dc`,
         `_features_rest`, `_opacity`, `_scaling` and `_rotation` keep only the anchored rows (in place on `gaussians`).
-        `keep` and `anchor_error` stay on the returned animator; **kw go to the constructor."""
+        `keep` and `anchor_error` stay on the returned animator; **kw go to the constructor.  repose_rotations=True binds
+        the culled `_rotation` (so that rows match) on `vertices`, the mesh the avatar was just anchored on."""
         anchors, keep, err = anchor_to_mesh(gaussians.get_xyz.detach(), vertices, faces, max_error=max_error)
         for name in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
             setattr(gaussians, name, getattr(gaussians, name)[keep])
+        if kw.get("repose_rotations"):
+            kw["rest_vertices"] = vertices
         anim = cls(gaussians, anchors, **kw)
         anim.keep, anim.anchor_error = keep, err
         return anim
 
     @torch.no_grad()
     def render_frame(self, vertices, camera) -> torch.Tensor:
+        if self.repose_rotations:                                            # opt-in: positions and rotations in one pass
+            self.gaussians._xyz, self.gaussians._rotation = self.anchors.positions_and_rotations(vertices)
+            return self.renderer.render(camera, antialiasing=self.antialiasing)["image"]
         self.gaussians._xyz = self.anchors.positions(vertices)               # animation.py:384-403, on the device
         return self.renderer.render(camera, antialiasing=self.antialiasing)["image"]      # animation.py:477-482
 

@@ -930,6 +930,24 @@ int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const i
   return HGS_OK;
 }
 
+int hgs_reanchor_rot(int32_t P, const float* vertices, const int32_t* faces, const int32_t* mapping_face,
+                     const float* mapping_uvw, const float* mapping_dist, const float* rot_in, int32_t bind, float* xyz,
+                     float* rot_out, void* stream_) {
+  if (P < 0) return HGS_EINVAL;
+  if (P == 0) return HGS_OK;
+  if (!vertices || !faces || !mapping_face || !mapping_uvw || !mapping_dist || !rot_in || !rot_out) return HGS_EINVAL;
+  if (!bind && !xyz) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (bind)
+    hipLaunchKernelGGL(hgs_k_reanchor_rot_bind, dim3((P + 255) / 256), dim3(256), 0, stream, (int)P, vertices, faces,
+                       mapping_face, mapping_uvw, mapping_dist, rot_in, xyz, rot_out);
+  else
+    hipLaunchKernelGGL(hgs_k_reanchor_rot_pose, dim3((P + 255) / 256), dim3(256), 0, stream, (int)P, vertices, faces,
+                       mapping_face, mapping_uvw, mapping_dist, rot_in, xyz, rot_out);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
 // One launch for every tensor of the call (optim.hip): tensor k gets one workgroup per HGS_ADAM_BLOCK_ELEMS elements; beyond
 // HGS_ADAM_MAX_BLOCKS in all, every tensor's share shrinks in proportion (at least one) and its workgroups grid-stride.
 int hgs_adam_step(const hgs_adam_args* args, void* stream_) {

@@ -164,3 +164,87 @@ hgs_k_reanchor(int P, const float* __restrict__ vertices, const int32_t* __restr
   xyz[3 * i + 1] = (ay * u + by * vv + cy * w) + d * ny;
   xyz[3 * i + 2] = (az * u + bz * vv + cz * w) + d * nz;
 }
+
+// ---- re-anchoring that also carries the rotations (opt-in; include/hgs_rast.h: hgs_reanchor_rot) -----------------
+// The frame of face (a, b, c):  e1 = (b-a)/|b-a|,  n = (b-a)x(c-a)/|.|,  e2 = n x e1,  F = [e1 e2 n] (columns);  r = a unit
+// quaternion (w,x,y,z) of F, taken from the largest of the four diagonal terms 1+-F00+-F11+-F22 (each is four times a squared
+// component, their sum is 4: the largest is >= 1, so no branch divides by a small number).  r = (1,0,0,0) where |b-a|^2 or
+// |(b-a)x(c-a)|^2 is below 1e-30 or not finite.  Every operation is rounded to fp32 in the order written (no contraction);
+// tests/reanchor_rot_reference.py restates it operation by operation.
+//   BIND:  rot_out = conj(r) (x) rot_in   (once per avatar, at the rest mesh; xyz is written only where given)
+//   else:  rot_out = r (x) rot_in,  xyz[i] = hgs_k_reanchor's expressions in hgs_k_reanchor's order (the same bits)
+// (x) is the Hamilton product.  One thread per Gaussian, the three vertices loaded once; no LDS, no atomics, no arrays (a
+// quaternion picked by index would live in scratch: the four candidates are picked by selects).
+template <bool BIND>
+__device__ __forceinline__ void hgs_reanchor_rot_body(int P, const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                                      const int32_t* __restrict__ mapping_face,
+                                                      const float* __restrict__ mapping_uvw,
+                                                      const float* __restrict__ mapping_dist, const float* __restrict__ rot_in,
+                                                      float* __restrict__ xyz, float* __restrict__ rot_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  const int f = mapping_face[i];
+  const int i0 = faces[3 * f + 0], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  const float ax = vertices[3 * i0], ay = vertices[3 * i0 + 1], az = vertices[3 * i0 + 2];
+  const float bx = vertices[3 * i1], by = vertices[3 * i1 + 1], bz = vertices[3 * i1 + 2];
+  const float cx = vertices[3 * i2], cy = vertices[3 * i2 + 1], cz = vertices[3 * i2 + 2];
+  const float e1x = bx - ax, e1y = by - ay, e1z = bz - az;
+  const float e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+  const float mx = e1y * e2z - e1z * e2y, my = e1z * e2x - e1x * e2z, mz = e1x * e2y - e1y * e2x;
+  const float mm = mx * mx + my * my + mz * mz;
+  if (!BIND || xyz) {                                           // hgs_k_reanchor, expression for expression
+    const float inv = 1.0f / (sqrtf(mm) + 1e-20f);
+    const float nx = mx * inv, ny = my * inv, nz = mz * inv;
+    const float u = mapping_uvw[3 * i], vv = mapping_uvw[3 * i + 1], w = mapping_uvw[3 * i + 2];
+    const float d = mapping_dist[i];
+    xyz[3 * i + 0] = (ax * u + bx * vv + cx * w) + d * nx;
+    xyz[3 * i + 1] = (ay * u + by * vv + cy * w) + d * ny;
+    xyz[3 * i + 2] = (az * u + bz * vv + cz * w) + d * nz;
+  }
+  const float ll = e1x * e1x + e1y * e1y + e1z * e1z;
+  // (a NaN fails both comparisons of its line: not finite -> the identity)
+  const bool sound = ll >= 1e-30f && ll <= 3.402823466e38f && mm >= 1e-30f && mm <= 3.402823466e38f;
+  float rw = 1.0f, rx = 0.0f, ry = 0.0f, rz = 0.0f;
+  if (sound) {
+    const float l = sqrtf(ll), m = sqrtf(mm);
+    const float f00 = e1x / l, f10 = e1y / l, f20 = e1z / l;                       // e1
+    const float f02 = mx / m, f12 = my / m, f22 = mz / m;                          // n
+    const float f01 = f12 * f20 - f22 * f10, f11 = f22 * f00 - f02 * f20, f21 = f02 * f10 - f12 * f00;   // e2 = n x e1
+    const float tw = ((1.0f + f00) + f11) + f22, tx = ((1.0f + f00) - f11) - f22;
+    const float ty = ((1.0f - f00) + f11) - f22, tz = ((1.0f - f00) - f11) + f22;
+    const bool pw = tw >= tx && tw >= ty && tw >= tz;
+    const bool px = !pw && tx >= ty && tx >= tz;
+    const bool py = !pw && !px && ty >= tz;
+    const float t = pw ? tw : (px ? tx : (py ? ty : tz));
+    const float s = sqrtf(t);
+    const float big = 0.5f * s, h = 0.5f / s;
+    const float dw = f21 - f12, dy = f02 - f20, dz = f10 - f01;                   // 4 w x, 4 w y, 4 w z
+    const float sxy = f01 + f10, sxz = f02 + f20, syz = f12 + f21;                // 4 x y, 4 x z, 4 y z
+    rw = pw ? big : (px ? dw : (py ? dy : dz)) * h;
+    rx = px ? big : (pw ? dw : (py ? sxy : sxz)) * h;
+    ry = py ? big : (pw ? dy : (px ? sxy : syz)) * h;
+    rz = (pw || px || py) ? (pw ? dz : (px ? sxz : syz)) * h : big;
+  }
+  if (BIND) { rx = -rx; ry = -ry; rz = -rz; }
+  const float qw = rot_in[4 * i], qx = rot_in[4 * i + 1], qy = rot_in[4 * i + 2], qz = rot_in[4 * i + 3];
+  rot_out[4 * i + 0] = ((rw * qw - rx * qx) - ry * qy) - rz * qz;
+  rot_out[4 * i + 1] = ((rw * qx + rx * qw) + ry * qz) - rz * qy;
+  rot_out[4 * i + 2] = ((rw * qy - rx * qz) + ry * qw) + rz * qx;
+  rot_out[4 * i + 3] = ((rw * qz + rx * qy) - ry * qx) + rz * qw;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+hgs_k_reanchor_rot_bind(int P, const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                        const int32_t* __restrict__ mapping_face, const float* __restrict__ mapping_uvw,
+                        const float* __restrict__ mapping_dist, const float* __restrict__ rot_in, float* __restrict__ xyz,
+                        float* __restrict__ rot_out) {
+  hgs_reanchor_rot_body<true>(P, vertices, faces, mapping_face, mapping_uvw, mapping_dist, rot_in, xyz, rot_out);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+hgs_k_reanchor_rot_pose(int P, const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                        const int32_t* __restrict__ mapping_face, const float* __restrict__ mapping_uvw,
+                        const float* __restrict__ mapping_dist, const float* __restrict__ rot_in, float* __restrict__ xyz,
+                        float* __restrict__ rot_out) {
+  hgs_reanchor_rot_body<false>(P, vertices, faces, mapping_face, mapping_uvw, mapping_dist, rot_in, xyz, rot_out);
+}

@@ -848,6 +848,29 @@ Tensor reanchor(const Tensor& vertices, const Tensor& faces, const Tensor& mappi
   return xyz;
 }
 
+// hgs_reanchor_rot on the current stream, nothing read back -> (xyz [P,3], rot [P,4]).  bind: rot = conj(r) (x) rot_in at the
+// rest mesh; else rot = r (x) rot_in at the posed mesh.  Both forms return the re-anchored positions.
+std::vector<Tensor> reanchor_rot(const Tensor& vertices, const Tensor& faces, const Tensor& mapping_face,
+                                 const Tensor& mapping_uvw, const Tensor& mapping_dist, const Tensor& rot_in, bool bind) {
+  at::NoGradGuard ng;
+  const c10::Device dev = vertices.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  const Tensor v = f32c(vertices, dev, "vertices"), uvw = f32c(mapping_uvw, dev, "mapping_uvw"), dist = f32c(mapping_dist, dev, "mapping_dist");
+  const Tensor q = f32c(rot_in, dev, "rot_in");
+  const Tensor f = faces.to(at::kInt).contiguous(), mf = mapping_face.to(at::kInt).contiguous();
+  if (f.device() != dev || mf.device() != dev) throw std::runtime_error("faces / mapping_face must live on the same device");
+  const int64_t P = mf.numel();
+  if (uvw.numel() != 3 * P || dist.numel() != P || q.numel() != 4 * P || v.numel() % 3 || f.numel() % 3)
+    throw std::runtime_error("reanchor_rot: inconsistent shapes");
+  Tensor xyz = at::empty({P, 3}, v.options()), rot = at::empty({P, 4}, v.options());
+  check_rc(hgs_reanchor_rot((int32_t)P, fptr(v), f.numel() ? f.data_ptr<int32_t>() : nullptr, P > 0 ? mf.data_ptr<int32_t>() : nullptr,
+                            fptr(uvw), fptr(dist), fptr(q), bind ? 1 : 0, fptr_mut(xyz), fptr_mut(rot),
+                            c10::hip::getCurrentHIPStream(dev.index()).stream()),
+           "hgs_reanchor_rot");
+  return {xyz, rot};
+}
+
 // ---- the optimizer step (include/hgs_rast.h: hgs_adam_step): every tensor of the lists in one launch per
 // HGS_ADAM_MAX_TENSORS of them, on the current stream, nothing read back.  scalars[k] = the six floats of tensor k in the
 // header's order (step_size, bc2_sqrt, w1, beta2, w2, eps), derived by the caller in double.  Nothing is converted or
@@ -1357,6 +1380,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("densify_masks", &densify_masks, py::call_guard<py::gil_scoped_release>());
   m.def("compact_rows", &compact_rows, py::call_guard<py::gil_scoped_release>());
   m.def("reanchor", &reanchor, py::call_guard<py::gil_scoped_release>());
+  m.def("reanchor_rot", &reanchor_rot, py::call_guard<py::gil_scoped_release>());
   m.def("adam_step", &adam_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
         py::arg("scalars"), py::arg("visible") = py::none(), py::call_guard<py::gil_scoped_release>());
   m.def("lbs_pose", &lbs_pose, py::arg("v_shaped"), py::arg("J_rest"), py::arg("parents"), py::arg("posedirs"),

@@ -368,6 +368,27 @@ int hgs_gather_rows(int64_t n_out, int32_t row_floats, const int32_t* src_of_dst
 int hgs_reanchor(int32_t P, const float* vertices, const int32_t* faces, const int32_t* mapping_face,
                  const float* mapping_uvw, const float* mapping_dist, float* xyz, void* stream);
 
+/* Re-anchoring that also carries the Gaussians' rotations with their anchor faces (v17, additive; opt-in: beyond the
+ * reference, which moves xyz only).  Quaternions are (w, x, y, z); R(q) is the reference's build_rotation
+ * (gaussiansplatting/utils/general_utils.py:78-99) of q / |q|; p (x) q is the Hamilton product, R(p (x) q) = R(p) R(q).
+ * Frame of a face with vertices a, b, c:
+ *   e1 = (b - a) / |b - a|,  n = (b - a) x (c - a) / |(b - a) x (c - a)|,  e2 = n x e1,  F = [e1 e2 n] (columns);
+ *   r(a, b, c) = a unit quaternion of F, converted from the largest of the four diagonal terms 1 +- F00 +- F11 +- F22 (no
+ *   branch divides by a small number); its sign is unspecified and nothing downstream depends on it.
+ *   r = (1, 0, 0, 0) if |b - a|^2 < 1e-30, |(b - a) x (c - a)|^2 < 1e-30, or either is not finite: a NaN or Inf vertex
+ *   never puts a NaN into a rotation (the position of such a row is whatever hgs_reanchor gives).
+ * bind != 0 (once per avatar, `vertices` = the rest mesh):  rot_out[i] = conj(r(face of i)) (x) rot_in[i];  xyz may be NULL
+ *   (written like hgs_reanchor where given).
+ * bind == 0 (every frame, `vertices` = the posed mesh):     rot_out[i] = r(face of i) (x) rot_in[i],  rot_in = what the
+ *   bind call returned;  xyz[i] = hgs_reanchor's value, bit for bit (same expressions, same order).
+ * rot_in is the RAW rotation parameter (not normalised): the products with unit quaternions keep its length, the caller's
+ * activation normalises as always.  All arithmetic is fp32, each operation rounded, no contraction.  Scales and colours are
+ * not re-posed.  rot_in / rot_out [P][4] fp32, the rest as hgs_reanchor.  P == 0: HGS_OK without a launch; P < 0 or a NULL
+ * required pointer with P > 0: HGS_EINVAL. */
+int hgs_reanchor_rot(int32_t P, const float* vertices, const int32_t* faces, const int32_t* mapping_face,
+                     const float* mapping_uvw, const float* mapping_dist, const float* rot_in, int32_t bind, float* xyz,
+                     float* rot_out, void* stream);
+
 /* ---- the optimizer step: Adam over every parameter tensor of the model in ONE launch -------------------------------
  * The reference builds torch.optim.Adam over six groups of one tensor each (gaussiansplatting/scene/gaussian_model.py:
  * 156-165): a chain of elementwise kernels per group and step.  hgs_adam_step updates up to HGS_ADAM_MAX_TENSORS tensors
