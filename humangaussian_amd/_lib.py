@@ -104,6 +104,15 @@ class HgsStepImagesArgs(Structure):
     ]
 
 
+class HgsFsampleArgs(Structure):
+    """ctypes mirror of `hgs_fsample_args` (hgs_fsample)."""
+    _fields_ = [
+        ("info_host", c_void_p), ("axis", c_void_p), ("plan", c_void_p), ("lists", c_void_p),
+        ("M", c_int32), ("normalized", c_int32), ("points", c_void_p), ("colors", c_void_p), ("scratch", c_void_p),
+        ("density", c_void_p), ("normal", c_void_p), ("color", c_void_p),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -182,6 +191,8 @@ EXPORTS = {
     "hgs_mc_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "hgs_mc_count": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "hgs_mc_emit": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float] + [c_void_p] * 5),
+    "hgs_fsample_scratch_bytes": (c_size_t, [c_int32, c_int32]),
+    "hgs_fsample": (ctypes.c_int, [POINTER(HgsFsampleArgs), c_void_p]),
 }
 
 

@@ -1362,6 +1362,73 @@ int hgs_field_eval(const hgs_field_info* info_host, const float* axis, const voi
   return HGS_OK;
 }
 
+namespace {
+// scratch of hgs_fsample: the table and the cursors first, as one piece (zeroed by one memset)
+struct FSampleCarve { size_t zeroed, zeroed_bytes, blk, bins, total; };
+FSampleCarve carve_fsample(int32_t M, int32_t nb) {
+  FSampleCarve c;
+  Carver cv;
+  const size_t nblocks = (size_t)nb * nb * nb;
+  c.zeroed_bytes = (nblocks + 1) * 8 + nblocks * 4;
+  c.zeroed = cv.take(c.zeroed_bytes);
+  c.blk = cv.take((size_t)M * 4);
+  c.bins = cv.take((size_t)M * 4);
+  c.total = cv.off;
+  return c;
+}
+}  // namespace
+
+size_t hgs_fsample_scratch_bytes(int32_t M, int32_t num_blocks) {
+  if (M < 0 || num_blocks < 1 || num_blocks > HGS_FIELD_MAX_BLOCKS) return 0;
+  return carve_fsample(M, num_blocks).total;
+}
+
+int hgs_fsample(const hgs_fsample_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_fsample_args& a = *args;
+  if (!field_info_ok(a.info_host) || a.M < 0 || (a.color && !a.colors)) return HGS_EINVAL;
+  if (a.M == 0 || (!a.density && !a.normal && !a.color)) return HGS_OK;
+  if (!a.points) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hgs_field_info& in = *a.info_host;
+  const size_t M = (size_t)a.M;
+  if (in.num_refs == 0) {                                   // every list is empty (and `lists` need not exist): zeros
+    hipError_t e = hipSuccess;
+    if (a.density) e = hipMemsetAsync(a.density, 0, M * 4, stream);
+    if (e == hipSuccess && a.normal) e = hipMemsetAsync(a.normal, 0, M * 12, stream);
+    if (e == hipSuccess && a.color) e = hipMemsetAsync(a.color, 0, M * 12, stream);
+    return hip_rc(e);
+  }
+  if (!a.axis || !a.plan || !a.lists || !a.scratch) return HGS_EINVAL;
+  const FieldDims D = {in.num_gaussians, in.resolution, in.num_blocks, in.resolution / in.num_blocks};
+  const FieldPlanPtrs pp = field_plan_ptrs(carve_field_plan(D.P, D.nb), const_cast<void*>(a.plan));
+  const FieldListCarve lc = carve_field_lists(D.nb, in.num_refs);
+  char* lb = static_cast<char*>(const_cast<void*>(a.lists));
+  const FieldListPtrs lp = {reinterpret_cast<uint32_t*>(lb + lc.start), reinterpret_cast<uint32_t*>(lb + lc.order),
+                            reinterpret_cast<uint32_t*>(lb + lc.refs)};
+  const uint32_t nblocks = (uint32_t)(D.nb * D.nb * D.nb);
+  const FSampleCarve sc = carve_fsample(a.M, D.nb);
+  char* sb = static_cast<char*>(a.scratch);
+  FSamplePtrs sp;
+  sp.tab = reinterpret_cast<uint2*>(sb + sc.zeroed);
+  sp.cursor = reinterpret_cast<uint32_t*>(sb + sc.zeroed + ((size_t)nblocks + 1) * 8);
+  sp.blk = reinterpret_cast<uint32_t*>(sb + sc.blk);
+  sp.bins = reinterpret_cast<uint32_t*>(sb + sc.bins);
+  const FSampleGeo geo = {in.center[0], in.center[1], in.center[2], in.scale, a.normalized ? 1 : 0};
+  const FSampleOut out = {a.density, a.normal, a.color};
+  const hipError_t e = hipMemsetAsync(sb + sc.zeroed, 0, sc.zeroed_bytes, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  const unsigned gm = (unsigned)((M + 255) / 256);
+  hipLaunchKernelGGL(hgs_k_fsample_bin, dim3(gm), dim3(256), 0, stream, D, (uint32_t)M, a.points, a.axis, geo, sp, out);
+  hipLaunchKernelGGL(hgs_k_fsample_table, dim3(1), dim3(1024), 0, stream, D, sp);
+  hipLaunchKernelGGL(hgs_k_fsample_scatter, dim3(gm), dim3(256), 0, stream, (uint32_t)M, sp);
+  // every block with points has at most one run that is not full: ceil(M / 256) + min(blocks, M) bounds the runs
+  const unsigned runs = gm + (unsigned)std::min<size_t>(nblocks, M);
+  hipLaunchKernelGGL(hgs_k_fsample_eval, dim3(runs), dim3(HGS_FSAMPLE_RUN), 0, stream, D, a.points, a.colors, geo, pp, lp, sp, out);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
 size_t hgs_mc_scratch_bytes(int32_t X, int32_t Y, int32_t Z) {
   if (!mc_dims_ok(X, Y, Z)) return 0;
   return carve_mc((size_t)X * Y * Z).total;

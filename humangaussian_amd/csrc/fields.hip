@@ -11,6 +11,9 @@
 //
 // Marching cubes:  count (crossing mask per grid point, triangles per cell) -> scan1/2/3 -> emit (vertices per crossed edge,
 // triangles per cell through the edge -> vertex map).
+//
+// Point samples (hgs_fsample: density, normal and colour at arbitrary points, over the lists hgs_field_eval left):
+//         bin (block per point, points per block) -> table (scan of points and of runs of 256) -> scatter -> eval
 #pragma once
 #include "hgs_common.h"
 
@@ -340,5 +343,160 @@ hgs_k_mc_emit(McDims D, const float* __restrict__ f, float thr, McPtrs p, uint32
       const uint32_t axis = e >> 3;
       triangles[3 * (size_t)t + c] = (int32_t)(p.offs[q].x + (uint32_t)__popc(p.mask[q] & ((1u << axis) - 1u)));
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ point samples
+
+#define HGS_FSAMPLE_RUN 256              // points of one evaluation workgroup, one per thread
+#define HGS_FSAMPLE_LDS_F4 4             // a staged record: the field's three float4 and the colour (64 B)
+
+struct FSamplePtrs {
+  uint32_t* blk;        // [M] block of the point, or HGS_FIELD_NONE (a coordinate that is not finite)
+  uint32_t* cursor;     // [nb^3] zeroed; the scatter's position inside a bin
+  uint2* tab;           // [nb^3 + 1] (points, runs) per block - counts (zeroed first), then exclusive offsets
+  uint32_t* bins;       // [M] point indices, block by block
+};
+struct FSampleGeo { float cx, cy, cz, scale; int32_t normalized; };
+struct FSampleOut { float* density; float* normal; float* color; };
+
+__device__ __forceinline__ float3 fsample_normalised(const float* __restrict__ points, uint32_t i, const FSampleGeo& geo) {
+  const float3 q = make_float3(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]);
+  if (geo.normalized) return q;
+  return make_float3((q.x - geo.cx) * geo.scale, (q.y - geo.cy) * geo.scale, (q.z - geo.cz) * geo.scale);
+}
+
+// (number of samples <= v) - 1, clamped to [0, R - 1]: the count runs over the samples 1 .. R - 1 (at most 11 steps)
+__device__ __forceinline__ int fsample_cell(const float* __restrict__ axis, int R, float v) {
+  int lo = 1, hi = R;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (axis[mid] <= v) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+hgs_k_fsample_bin(FieldDims D, uint32_t M, const float* __restrict__ points, const float* __restrict__ axis, FSampleGeo geo,
+                  FSamplePtrs sp, FSampleOut out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= M) return;
+  const float3 n = fsample_normalised(points, i, geo);
+  if (!(isfinite(n.x) && isfinite(n.y) && isfinite(n.z))) {
+    sp.blk[i] = HGS_FIELD_NONE;                            // no workgroup of the evaluation sees it: its zeros are written here
+    if (out.density) out.density[i] = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (out.normal) out.normal[3 * (size_t)i + a] = 0.0f;
+      if (out.color) out.color[3 * (size_t)i + a] = 0.0f;
+    }
+    return;
+  }
+  const uint32_t bx = (uint32_t)(fsample_cell(axis, D.R, n.x) / D.split), by = (uint32_t)(fsample_cell(axis, D.R, n.y) / D.split),
+                 bz = (uint32_t)(fsample_cell(axis, D.R, n.z) / D.split);
+  const uint32_t block = (bx * (uint32_t)D.nb + by) * (uint32_t)D.nb + bz;
+  sp.blk[i] = block;
+  atomicAdd(&sp.tab[block].x, 1u);
+}
+
+// one workgroup: tab[] = exclusive scan of (points, runs of HGS_FSAMPLE_RUN points) per block, the totals behind the end
+extern "C" __global__ void __launch_bounds__(1024)
+hgs_k_fsample_table(FieldDims D, FSamplePtrs sp) {
+  const uint32_t nblocks = (uint32_t)(D.nb * D.nb * D.nb);
+  for (uint32_t b = threadIdx.x; b < nblocks; b += 1024u)          // (thread b % 1024 also scans element b)
+    sp.tab[b].y = (sp.tab[b].x + (HGS_FSAMPLE_RUN - 1u)) / HGS_FSAMPLE_RUN;
+  const uint2 total = hgs_scan_carry(nblocks, sp.tab, sp.tab);
+  if (threadIdx.x == 0) sp.tab[nblocks] = total;
+}
+
+// where a point stands inside its bin changes no result: every point's sums are its own
+extern "C" __global__ void __launch_bounds__(256)
+hgs_k_fsample_scatter(uint32_t M, FSamplePtrs sp) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= M) return;
+  const uint32_t block = sp.blk[i];
+  if (block == HGS_FIELD_NONE) return;
+  sp.bins[sp.tab[block].x + atomicAdd(&sp.cursor[block], 1u)] = i;
+}
+
+// A workgroup takes one run of a block's bin, a thread one point.  The launch has the host's upper bound of runs; the
+// table says which (block, run) a workgroup is, and the surplus leaves.  The records go through LDS as in
+// hgs_k_field_eval, with the colour in a fourth float4, and the power is spelled as there: a point on a grid sample gets
+// the field's bits.  t = (2A dx + B dy + C dz, B dx + 2D dy + E dz, C dx + E dy + 2F dz) is the gradient of the folded
+// form, so G = - sum of o e t.
+extern "C" __global__ void __launch_bounds__(256)
+hgs_k_fsample_eval(FieldDims D, const float* __restrict__ points, const float* __restrict__ colors, FSampleGeo geo,
+                   FieldPlanPtrs pp, FieldListPtrs lp, FSamplePtrs sp, FSampleOut out) {
+  __shared__ float4 st[HGS_FIELD_CHUNK * HGS_FSAMPLE_LDS_F4];
+  const uint32_t nblocks = (uint32_t)(D.nb * D.nb * D.nb);
+  const uint32_t w = blockIdx.x;
+  if (w >= sp.tab[nblocks].y) return;
+  uint32_t lo = 0, hi = nblocks;                            // the last block whose first run is <= w (empty blocks in front of
+  while (hi - lo > 1u) {                                    // it share its offset and are passed over)
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sp.tab[mid].y <= w) lo = mid; else hi = mid;
+  }
+  const uint32_t block = lo;
+  const uint2 at = sp.tab[block];
+  const uint32_t j = (w - at.y) * HGS_FSAMPLE_RUN + threadIdx.x;
+  const bool live = j < sp.tab[block + 1].x - at.x;
+  const uint32_t i = live ? sp.bins[at.x + j] : 0u;
+  float3 p = make_float3(0.0f, 0.0f, 0.0f);
+  if (live) p = fsample_normalised(points, i, geo);
+  const uint32_t first = lp.start[block], n = lp.start[block + 1] - first;
+  float acc = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+  for (uint32_t c0 = 0; c0 < n; c0 += HGS_FIELD_CHUNK) {
+    const uint32_t cn = min((uint32_t)HGS_FIELD_CHUNK, n - c0);
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < cn; r += blockDim.x) {
+      const uint32_t g = lp.refs[first + c0 + r];
+      const float2* __restrict__ rec = pp.rec + (size_t)g * (HGS_FIELD_REC_FLOATS / 2);
+      const float2 a = rec[0], b = rec[1], c = rec[2], d = rec[3], e = rec[4];
+      st[r * HGS_FSAMPLE_LDS_F4 + 0] = make_float4(a.x, a.y, b.x, b.y);     // nx ny nz A
+      st[r * HGS_FSAMPLE_LDS_F4 + 1] = make_float4(c.x, c.y, d.x, d.y);     // B C D E
+      st[r * HGS_FSAMPLE_LDS_F4 + 2] = make_float4(e.x, e.y, 0.0f, 0.0f);   // F opacity
+      st[r * HGS_FSAMPLE_LDS_F4 + 3] = colors ? make_float4(colors[3 * (size_t)g], colors[3 * (size_t)g + 1], colors[3 * (size_t)g + 2], 0.0f)
+                                              : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    __syncthreads();
+    for (uint32_t r = 0; r < cn; ++r) {
+      const float4 u = st[r * HGS_FSAMPLE_LDS_F4 + 0], v = st[r * HGS_FSAMPLE_LDS_F4 + 1], k = st[r * HGS_FSAMPLE_LDS_F4 + 2],
+                   col = st[r * HGS_FSAMPLE_LDS_F4 + 3];
+      const float dy = p.y - u.y, dz = p.z - u.z;
+      const float q1 = __builtin_fmaf(v.x, dy, v.y * dz);                                   // B dy + C dz
+      const float q0 = __builtin_fmaf(dy, __builtin_fmaf(v.z, dy, v.w * dz), (k.x * dz) * dz);   // D dy^2 + E dy dz + F dz^2
+      const float dx = p.x - u.x;
+      const float pw = __builtin_fmaf(dx, __builtin_fmaf(u.w, dx, q1), q0);
+      const float e = pw > 0.0f ? 0.0f : __builtin_amdgcn_exp2f(pw);
+      acc = __builtin_fmaf(k.y, e, acc);
+      const float oe = k.y * e;
+      const float tx = __builtin_fmaf(u.w + u.w, dx, q1);
+      const float ty = __builtin_fmaf(v.x, dx, __builtin_fmaf(v.z + v.z, dy, v.w * dz));
+      const float tz = __builtin_fmaf(v.y, dx, __builtin_fmaf(v.w, dy, (k.x + k.x) * dz));
+      sx = __builtin_fmaf(oe, tx, sx);
+      sy = __builtin_fmaf(oe, ty, sy);
+      sz = __builtin_fmaf(oe, tz, sz);
+      cr = __builtin_fmaf(oe, col.x, cr);
+      cg = __builtin_fmaf(oe, col.y, cg);
+      cb = __builtin_fmaf(oe, col.z, cb);
+    }
+  }
+  if (!live) return;
+  if (out.density) out.density[i] = acc;
+  if (out.normal) {
+    // scaled by the largest component first: the squares of a G that is finite and not zero neither underflow nor overflow
+    const float m = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
+    const bool ok = m > 0.0f && isfinite(sx) && isfinite(sy) && isfinite(sz);
+    const float ux = sx / m, uy = sy / m, uz = sz / m;
+    const float inv = -1.0f / sqrtf((ux * ux + uy * uy) + uz * uz);
+    out.normal[3 * (size_t)i] = ok ? ux * inv : 0.0f;
+    out.normal[3 * (size_t)i + 1] = ok ? uy * inv : 0.0f;
+    out.normal[3 * (size_t)i + 2] = ok ? uz * inv : 0.0f;
+  }
+  if (out.color) {
+    const bool any = acc != 0.0f;
+    out.color[3 * (size_t)i] = any ? cr / acc : 0.0f;
+    out.color[3 * (size_t)i + 1] = any ? cg / acc : 0.0f;
+    out.color[3 * (size_t)i + 2] = any ? cb / acc : 0.0f;
   }
 }

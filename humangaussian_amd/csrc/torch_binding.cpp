@@ -1280,7 +1280,17 @@ std::tuple<Tensor, Tensor, c10::optional<Tensor>> mesh_query(const Tensor& point
 // ---- density field and marching cubes (include/hgs_rast.h: hgs_field_*, hgs_mc_*; the reference's extract_fields / mcubes) ----
 // (occ [R, R, R] fp32, block counts [nb, nb, nb] int32 or undefined, [center x, y, z, extent, scale], [num_kept, num_refs]).
 // One host wait (the plan's header sizes the lists).  Nothing kept: a zero field and no evaluation.
-std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64_t>> field_extract(
+// (`plan`, `lists` and `info` are what hgs_fsample needs to evaluate the same field at other points; lists stays undefined
+// where nothing is listed.)
+struct FieldBuilt {
+  Tensor occ;
+  c10::optional<Tensor> counts;
+  std::vector<double> geo;
+  std::vector<int64_t> sizes;
+  Tensor plan, lists;
+  hgs_field_info info;
+};
+FieldBuilt field_build_impl(
     const Tensor& xyz, const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, const Tensor& axis,
     int64_t num_blocks, double grow, bool want_counts) {
   at::NoGradGuard ng;
@@ -1315,7 +1325,7 @@ std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64
   const std::vector<int64_t> sizes = {(int64_t)info.num_kept, (int64_t)info.num_refs};
   if (info.num_refs == 0) {
     if (want_counts) counts = at::zeros({num_blocks, num_blocks, num_blocks}, opts.dtype(at::kInt));
-    return {at::zeros({R, R, R}, opts.dtype(at::kFloat)), counts, geo, sizes};
+    return {at::zeros({R, R, R}, opts.dtype(at::kFloat)), counts, geo, sizes, plan, Tensor(), info};
   }
   const size_t bytes = hgs_field_list_bytes(&info);
   if (bytes == 0)
@@ -1326,7 +1336,78 @@ std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64
   if (want_counts) counts = at::empty({num_blocks, num_blocks, num_blocks}, opts.dtype(at::kInt));
   check_rc(hgs_field_eval(&info, fptr(ax), plan.data_ptr(), lists.data_ptr(), occ.data_ptr<float>(),
                           want_counts ? counts->data_ptr<int32_t>() : nullptr, stream), "hgs_field_eval");
-  return {occ, counts, geo, sizes};
+  return {occ, counts, geo, sizes, plan, lists, info};
+}
+
+std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64_t>> field_extract(
+    const Tensor& xyz, const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, const Tensor& axis,
+    int64_t num_blocks, double grow, bool want_counts) {
+  FieldBuilt b = field_build_impl(xyz, opacity, scaling, rotation, axis, num_blocks, grow, want_counts);
+  return {b.occ, b.counts, b.geo, b.sizes};
+}
+
+// field_extract's results, then what a later field_sample needs: plan, lists (no element where nothing is listed) and the
+// plan's header as 72 bytes on the host
+std::tuple<Tensor, c10::optional<Tensor>, std::vector<double>, std::vector<int64_t>, Tensor, Tensor, Tensor> field_build(
+    const Tensor& xyz, const Tensor& opacity, const Tensor& scaling, const Tensor& rotation, const Tensor& axis,
+    int64_t num_blocks, double grow, bool want_counts) {
+  FieldBuilt b = field_build_impl(xyz, opacity, scaling, rotation, axis, num_blocks, grow, want_counts);
+  Tensor info = at::empty({(int64_t)sizeof(hgs_field_info)}, at::TensorOptions().dtype(at::kByte));
+  memcpy(info.data_ptr(), &b.info, sizeof(hgs_field_info));
+  if (!b.lists.defined()) b.lists = at::empty({0}, at::TensorOptions().device(xyz.device()).dtype(at::kByte));
+  return {b.occ, b.counts, b.geo, b.sizes, b.plan, b.lists, info};
+}
+
+// (density [M], normal [M, 3], color [M, 3] or undefined) of the field at `points`; no host wait
+std::tuple<Tensor, Tensor, c10::optional<Tensor>> field_sample(
+    const Tensor& info, const Tensor& axis, const Tensor& plan, const Tensor& lists, const Tensor& points,
+    const c10::optional<Tensor>& colors, bool normalized) {
+  at::NoGradGuard ng;
+  const c10::Device dev = points.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  if (points.dim() != 2 || points.size(1) != 3) throw std::runtime_error("points must have dimensions (M, 3)");
+  if (info.device().is_cuda() || info.scalar_type() != at::kByte || !info.is_contiguous() ||
+      info.numel() != (int64_t)sizeof(hgs_field_info))
+    throw std::runtime_error("field_sample: info is the header field_build returned");
+  hgs_field_info in;
+  memcpy(&in, info.data_ptr(), sizeof(in));
+  const int64_t M = points.size(0);
+  if (M > 0x7fffffffll / 16) throw std::runtime_error("too many points");
+  if (axis.dim() != 1 || axis.numel() != in.resolution) throw std::runtime_error("axis must have dimensions (resolution,)");
+  if (plan.device() != dev || lists.device() != dev || axis.device() != dev)
+    throw std::runtime_error("field_sample: the field and the points live on different devices");
+  if ((size_t)plan.numel() != hgs_field_plan_bytes(in.num_gaussians, in.num_blocks))
+    throw std::runtime_error("field_sample: plan does not belong to info");
+  if (in.num_refs > 0 && (size_t)lists.numel() != hgs_field_list_bytes(&in))
+    throw std::runtime_error("field_sample: lists do not belong to info");
+  if (colors && (colors->dim() != 2 || colors->size(0) != in.num_gaussians || colors->size(1) != 3))
+    throw std::runtime_error("colors must have dimensions (P, 3)");
+  DeviceSwitch guard(dev.index());
+  const auto opts = at::TensorOptions().device(dev).dtype(at::kFloat);
+  const Tensor pts = f32c(points, dev, "points"), ax = f32c(axis, dev, "axis");
+  Tensor col;
+  if (colors) col = f32c(*colors, dev, "colors");
+  Tensor density = at::empty({M}, opts), normal = at::empty({M, 3}, opts);
+  c10::optional<Tensor> color;
+  if (colors) color = at::empty({M, 3}, opts);
+  if (M == 0) return {density, normal, color};
+  Tensor scratch = at::empty({(int64_t)hgs_fsample_scratch_bytes((int32_t)M, in.num_blocks)}, opts.dtype(at::kByte));
+  hgs_fsample_args a;
+  memset(&a, 0, sizeof(a));
+  a.info_host = &in;
+  a.axis = fptr(ax);
+  a.plan = plan.data_ptr();
+  a.lists = lists.numel() ? lists.data_ptr() : nullptr;
+  a.M = (int32_t)M;
+  a.normalized = normalized ? 1 : 0;
+  a.points = fptr(pts);
+  a.colors = colors ? fptr(col) : nullptr;
+  a.scratch = scratch.data_ptr();
+  a.density = density.data_ptr<float>();
+  a.normal = normal.data_ptr<float>();
+  a.color = colors ? color->data_ptr<float>() : nullptr;
+  check_rc(hgs_fsample(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_fsample");
+  return {density, normal, color};
 }
 
 // (vertices [V, 3] fp32 in index coordinates, triangles [T, 3] int32); one host wait for the two sizes
@@ -1401,6 +1482,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("field_extract", &field_extract, py::arg("xyz"), py::arg("opacity"), py::arg("scaling"), py::arg("rotation"),
         py::arg("axis"), py::arg("num_blocks"), py::arg("grow"), py::arg("want_counts") = false,
         py::call_guard<py::gil_scoped_release>());
+  m.def("field_build", &field_build, py::arg("xyz"), py::arg("opacity"), py::arg("scaling"), py::arg("rotation"),
+        py::arg("axis"), py::arg("num_blocks"), py::arg("grow"), py::arg("want_counts") = false,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("field_sample", &field_sample, py::arg("info"), py::arg("axis"), py::arg("plan"), py::arg("lists"), py::arg("points"),
+        py::arg("colors") = py::none(), py::arg("normalized") = false, py::call_guard<py::gil_scoped_release>());
   m.def("marching_cubes", &marching_cubes, py::arg("field"), py::arg("threshold"), py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);

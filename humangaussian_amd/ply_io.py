@@ -82,5 +82,46 @@ def load_ply(path, max_sh_degree=None, kiui_axes=False):
                 scaling=scaling, rotation=rotation, max_sh_degree=deg)
 
 
+def save_mesh_ply(path, vertices, faces, normals=None, colors=None):
+    """A triangle mesh as a `binary_little_endian 1.0` PLY (what `fields.extract_mesh` returns; torch tensors or arrays).
+    Vertex properties: float x y z; float nx ny nz if `normals` (V,3) is given; uchar red green blue =
+    round(clamp(c, 0, 1) * 255) if `colors` (V,3) is given.  Faces: `property list uchar int vertex_indices`."""
+    arr = lambda a, dt: np.ascontiguousarray((a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)), dtype=dt)  # noqa: E731
+    v, f = arr(vertices, np.float32).reshape(-1, 3), arr(faces, np.int32).reshape(-1, 3)
+    fields_ = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {len(v)}\n" + \
+        "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        n = arr(normals, np.float32).reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"save_mesh_ply: {len(n)} normals for {len(v)} vertices")
+        fields_ += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        c = arr(colors, np.float32).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"save_mesh_ply: {len(c)} colors for {len(v)} vertices")
+        fields_ += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n"
+    rows = np.zeros(len(v), dtype=fields_)
+    for k, name in enumerate("xyz"):
+        rows[name] = v[:, k]
+    if normals is not None:
+        for k, name in enumerate(("nx", "ny", "nz")):
+            rows[name] = n[:, k]
+    if colors is not None:
+        with np.errstate(invalid="ignore"):
+            c8 = np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+        for k, name in enumerate(("red", "green", "blue")):
+            rows[name] = c8[:, k]
+    tri = np.zeros(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    tri["n"], tri["i"] = 3, f
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(rows.tobytes())
+        out.write(tri.tobytes())
+
+
 def math_sqrt(x):
     return float(np.sqrt(x))

@@ -746,6 +746,56 @@ int hgs_mc_count(const float* field, int32_t X, int32_t Y, int32_t Z, float thre
 int hgs_mc_emit(const float* field, int32_t X, int32_t Y, int32_t Z, float threshold, const void* scratch,
                 const hgs_mc_info* info_host, float* vertices, int32_t* triangles, void* stream);
 
+/* ---- the field at arbitrary points: density, outward normal and colour (vertex attributes of the extracted mesh) -------
+ * An extension: the reference's extract_mesh stops at (vertices, faces).  hgs_fsample evaluates the field of hgs_field_*
+ * at M points instead of at the grid samples, over the SAME per-block lists.  This definition is the contract:
+ *   Inputs: `info_host`, `axis`, `plan` and `lists` of a field as hgs_field_eval was given them and left them; points
+ *   [M][3] fp32; optionally colors [P][3] fp32, indexed by the ORIGINAL Gaussian index (P = the plan's num_gaussians).
+ *   For a point q:
+ *   1. n = (q - center) * scale in fp32, a subtraction then a multiplication (what the plan applies to a centre);
+ *      normalized != 0: n = q untouched (the caller already has normalised coordinates, e.g. grid positions).
+ *   2. a component of n that is not finite: every output of the point is 0.
+ *   3. per axis g = (number of axis samples <= n_a) - 1, clamped to [0, resolution - 1]; the block is g / (resolution /
+ *      num_blocks).  A point exactly on a grid sample belongs to that sample's block; a point outside the grid uses
+ *      the edge block.  (`axis` ascending, as torch.linspace gives it.)
+ *   4. over the block's list, in ASCENDING Gaussian index, with d = n - centre_i and e_i = exp(power_i) exactly as in the
+ *      field (exp2 of the folded form; 0 where the form is > 0):
+ *        density = sum o_i e_i                       - at a point that IS a grid sample: occ there, bit for bit
+ *        G       = sum o_i e_i Sigma_i^-1 d          - minus the gradient of the density, up to the positive constant of
+ *                                                      the folding: in the record's terms, proportional to
+ *                  -(2A dx + B dy + C dz, B dx + 2D dy + E dz, C dx + E dy + 2F dz)
+ *        normal  = G / |G|, or (0, 0, 0) where G is 0 or not finite.  |G| is formed after G is divided by its largest
+ *                  component, so the squares neither underflow nor overflow: every normal is a unit vector or zero.  It
+ *                  points from high density to low - the side the marching-cubes triangles face - and is the same in
+ *                  world space (the normalisation is a uniform scale).
+ *        color   = (sum o_i e_i c_i) / density, or (0, 0, 0) where density is 0.
+ *      A block with an empty list: zeros.
+ *   5. fp32 throughout; each point's sums are its own, one fixed instruction sequence: the outputs are bit-reproducible
+ *      from call to call and do not depend on where the point stands in the input.  No floating-point atomics (the
+ *      binning counts with integer atomics; a point's place in its bin changes no result).
+ * density [M], normal [M][3], color [M][3]: each optional (NULL: not computed); color requires colors.
+ * scratch: hgs_fsample_scratch_bytes(M, num_blocks) bytes (host arithmetic; 0 for M < 0 or num_blocks outside 1 .. 32).
+ * No host wait.  HGS_EINVAL before any launch for args == NULL, M < 0, color without colors, an info that
+ * hgs_field_list_bytes refuses, or a NULL among the pointers the call needs.  M == 0 launches nothing.  A plan without
+ * list entries (num_refs == 0; `lists` may then be NULL) gives zeros.
+ * v17 gained these exports without a change of any earlier signature. */
+typedef struct hgs_fsample_args {
+  const hgs_field_info* info_host;
+  const float* axis;                /* [resolution] */
+  const void* plan;
+  const void* lists;
+  int32_t M;
+  int32_t normalized;               /* points are normalised coordinates already */
+  const float* points;              /* [M][3] */
+  const float* colors;              /* [P][3] or NULL */
+  void* scratch;
+  float* density;                   /* [M] or NULL */
+  float* normal;                    /* [M][3] or NULL */
+  float* color;                     /* [M][3] or NULL */
+} hgs_fsample_args;
+size_t hgs_fsample_scratch_bytes(int32_t M, int32_t num_blocks);
+int hgs_fsample(const hgs_fsample_args* args, void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
