@@ -7,6 +7,7 @@ Only what the rasterize hot path needs:
   renderer.py      render() / Renderer.render() mirrors (the reference's two call sites)
   view_parallel.py view-parallel multi-GPU rendering (one RCCL all-gather per step)
   step_images.py   guidance_images(): the guidance's two images and the opacity losses of a step
+  surface.py       SurfaceSampler / create_from_pcd: the body surface sampled and the initial Gaussians built on the device
   synth.py         synthetic SMPL-X-like clouds + threestudio-style cameras (bench/tests)
 """
 from .rasterizer import (  # noqa: F401
@@ -17,6 +18,14 @@ from .rasterizer import (  # noqa: F401
 )
 
 from .step_images import StepImages, guidance_images  # noqa: F401
+from .surface import (  # noqa: F401
+    SurfaceSampler,
+    create_from_pcd,
+    create_from_points,
+    init_from_body,
+    sample_surface,
+)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
-           "rasterize_gaussians_batch", "StepImages", "guidance_images"]
+           "rasterize_gaussians_batch", "StepImages", "guidance_images", "SurfaceSampler", "sample_surface",
+           "create_from_points", "create_from_pcd", "init_from_body"]

@@ -113,6 +113,23 @@ class HgsFsampleArgs(Structure):
     ]
 
 
+SURFACE_MAX_FACES = (1 << 20) - 1
+
+
+class HgsSurfaceInfo(Structure):
+    """ctypes mirror of `hgs_surface_info` (the 16 bytes hgs_surface_cdf leaves on the device)."""
+    _fields_ = [("area", ctypes.c_double), ("num_positive", c_uint32), ("reserved", c_uint32)]
+
+
+class HgsSurfaceSampleArgs(Structure):
+    """ctypes mirror of `hgs_surface_sample_args` (hgs_surface_sample)."""
+    _fields_ = [
+        ("V", c_int32), ("F", c_int32), ("vertices", c_void_p), ("faces", c_void_p), ("cdf", c_void_p),
+        ("N", c_int64), ("offset", ctypes.c_uint64), ("seed", ctypes.c_uint64),
+        ("points", c_void_p), ("face", c_void_p), ("uvw", c_void_p),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -193,6 +210,10 @@ EXPORTS = {
     "hgs_mc_emit": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float] + [c_void_p] * 5),
     "hgs_fsample_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "hgs_fsample": (ctypes.c_int, [POINTER(HgsFsampleArgs), c_void_p]),
+    "hgs_surface_cdf_scratch_bytes": (c_size_t, [c_int32]),
+    "hgs_surface_cdf": (ctypes.c_int, [c_int32, c_void_p, c_int32] + [c_void_p] * 5),
+    "hgs_surface_sample": (ctypes.c_int, [POINTER(HgsSurfaceSampleArgs), c_void_p]),
+    "hgs_init_gaussians": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 9),
 }
 
 

@@ -30,6 +30,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "lbs.hip"
 #include "pose.hip"
 #include "step_images.hip"
+#include "surface.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -1472,6 +1473,76 @@ int hgs_mark_visible(const hgs_settings* s, int32_t P, const float* means3D, uin
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_mark_visible, dim3((P + HGS_BLOCK - 1) / HGS_BLOCK), dim3(HGS_BLOCK),
                      0, stream, s->viewmatrix, (int)P, means3D, present);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+// ---- surface samples and the initial Gaussians (surface.hip) ------------------------------------------------------------
+size_t hgs_surface_cdf_scratch_bytes(int32_t F) {
+  if (F < 1 || F > HGS_SURFACE_MAX_FACES) return 0;
+  return hgs_align_up(scan_shape((size_t)F + 1, 8).bsum_bytes, ALIGN);
+}
+
+int hgs_surface_cdf(int32_t V, const float* vertices, int32_t F, const int32_t* faces, double* cdf, hgs_surface_info* info,
+                    void* scratch, void* stream_) {
+  static_assert(sizeof(hgs_surface_info) == 16 && sizeof(SurfInfo) == 16, "the info block is 16 bytes");
+  if (V < 0 || F < 1 || F > HGS_SURFACE_MAX_FACES || !faces || !cdf || !info || !scratch || (V > 0 && !vertices)) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hipError_t e = hipMemsetAsync(info, 0, sizeof(hgs_surface_info), stream);
+  if (e != hipSuccess) return hip_rc(e);
+  // (F + 1 <= 2^20 entries: at most 1024 blocks, so the carry is ONE left-to-right round over their totals)
+  const unsigned nb = scan_shape((size_t)F + 1, 8).blocks;
+  double* bsum = static_cast<double*>(scratch);
+  hipLaunchKernelGGL(hgs_k_surface_area, dim3(nb), dim3(HGS_SCAN_BLOCK), 0, stream, (int)V, (uint32_t)F, vertices, faces, cdf, bsum);
+  hipLaunchKernelGGL(hgs_k_surface_carry, dim3(1), dim3(HGS_SCAN_BLOCK), 0, stream, (uint32_t)nb, bsum);
+  hipLaunchKernelGGL(hgs_k_surface_prefix, dim3(nb), dim3(HGS_SCAN_BLOCK), 0, stream, (uint32_t)F, cdf, (const double*)bsum,
+                     reinterpret_cast<SurfInfo*>(info));
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_surface_sample(const hgs_surface_sample_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_surface_sample_args& a = *args;
+  if (a.N < 0 || a.V < 0 || a.F < 1 || a.F > HGS_SURFACE_MAX_FACES || !a.faces || !a.cdf || (a.V > 0 && !a.vertices))
+    return HGS_EINVAL;
+  if (a.N == 0 || (!a.points && !a.face && !a.uvw)) return HGS_OK;
+  if ((uint64_t)a.N > 0xffffffffull * HGS_SURF_THREADS) return HGS_EINVAL;
+  SurfSampleArgs k;
+  k.V = a.V; k.F = a.F;
+  // every 2^shift-th entry of the table goes to LDS: the smallest shift >= 4 that fits the staging array
+  k.shift = 4;
+  while ((((size_t)a.F + 1) + ((size_t)1 << k.shift) - 1) >> k.shift > HGS_SURF_COARSE_MAX) ++k.shift;
+  k.ncoarse = (int32_t)((((size_t)a.F + 1) + ((size_t)1 << k.shift) - 1) >> k.shift);
+  k.vtx = a.vertices; k.faces = a.faces; k.cdf = a.cdf;
+  k.N = (unsigned long long)a.N; k.offset = a.offset;
+  k.seed_lo = (uint32_t)a.seed; k.seed_hi = (uint32_t)(a.seed >> 32);
+  k.points = a.points; k.face = a.face; k.uvw = a.uvw;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_surface_sample, dim3((unsigned)((k.N + HGS_SURF_THREADS - 1) / HGS_SURF_THREADS)),
+                     dim3(HGS_SURF_THREADS), 0, stream, k);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_init_gaussians(int64_t P, int32_t M, const float* colors, const float* dist2, float* features_dc,
+                       float* features_rest, float* scaling, float* rotation, float* opacity, float* max_radii2D,
+                       void* stream_) {
+  if (P < 0 || M < 1 || M > 4096) return HGS_EINVAL;
+  if (P == 0) return HGS_OK;
+  if (scaling && !dist2) return HGS_EINVAL;
+  InitGaussiansArgs k;
+  k.P = P;
+  k.rest_floats = 3 * (M - 1);
+  const float q = 0.1f / (1.0f - 0.1f);
+  k.opacity = (float)log((double)q);
+  k.colors = colors; k.dist2 = dist2;
+  k.features_dc = features_dc; k.features_rest = M > 1 ? features_rest : nullptr; k.scaling = scaling; k.rotation = rotation;
+  k.opacity_out = opacity; k.max_radii2D = max_radii2D;
+  const long long n = (long long)P * (12 + k.rest_floats);
+  if ((n + 255) / 256 > 0x7fffffffll) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_init_gaussians, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

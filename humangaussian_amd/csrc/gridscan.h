@@ -5,7 +5,8 @@
 //   float keys   hgs_float_key / hgs_key_float: unsigned images of floats with the same order (atomicMin / atomicMax)
 //   box          hgs_box_reduce: wave min / max of the points a lane takes, one atomic per wave, axis and bound
 //   scan         hgs_scan_totals -> hgs_scan_carry -> hgs_scan_prefix: the device-wide exclusive scan over 1024-element
-//                blocks, for uint32_t and for the uint2 pair marching cubes scans
+//                blocks, for uint32_t, for the uint2 pair marching cubes scans and for double (the surface sampler's
+//                table of face areas: sums in element order)
 //
 // The grid fit and the cell index are plain C++ (no HIP types), like cellmask.h: the SAME functions are compiled into the
 // kernels and into the host-side checker tests/gridfit_host.cpp.  cbrtf stays with the callers (their first cell edge h0),
@@ -81,7 +82,7 @@ __device__ __forceinline__ void hgs_box_reduce(bool take, float x, float y, floa
 }
 
 // ---- device-wide exclusive scan ------------------------------------------------------------------------------------------
-// Three launches of HGS_SCAN_BLOCK threads over v[0 .. n), T = uint32_t or uint2 (both components at once):
+// Three launches of HGS_SCAN_BLOCK threads over v[0 .. n), T = uint32_t, uint2 (both components at once) or double:
 //   1  hgs_scan_totals   ceil(n / 1024) workgroups: bsum[block] = the block's total
 //   2  hgs_scan_carry    ONE workgroup: bsum -> exclusive, 1024 totals a round with the carry in a register; returns the
 //                        grand total to every thread (also the whole scan of a short array: hgs_k_field_order)
@@ -96,11 +97,41 @@ __device__ __forceinline__ uint2 hgs_scan_1k(uint2 v, uint32_t* wtot, uint2& tot
   return make_uint2(ex, ey);
 }
 
+// T = double (surface.hip: the table of face areas): the workgroup's prefixes are the LEFT-TO-RIGHT sums
+// ((v0 + v1) + v2) + ..., element by element - the waves take turns, each continues the sum where the wave in front left
+// it.  That order is what makes a table of non-negative addends usable as it stands: the prefixes never decrease, and
+// a zero addend repeats the prefix in front of it bit for bit.  (A tree of partial sums promises neither.)  1024 dependent
+// additions per workgroup, some microseconds: for tables built once, not for a hot path.
+__device__ __forceinline__ double hgs_scan_1k(double v, double* wtot, double& tot) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int vlo = __double2loint(v), vhi = __double2hiint(v);
+  double ex = 0.0;
+  __syncthreads();                 // protect wtot from a previous use
+  for (int r = 0; r < (int)(HGS_SCAN_BLOCK / 64); ++r) {
+    if (w == r) {
+      double run = r ? wtot[r - 1] : 0.0;
+#pragma unroll 4                   // (all 64 at once keep 128 lane values in scalar registers and spill)
+      for (int k = 0; k < 64; ++k) {
+        if (lane == k) ex = run;
+        run += __hiloint2double(__builtin_amdgcn_readlane(vhi, k), __builtin_amdgcn_readlane(vlo, k));
+      }
+      if (lane == 0) wtot[r] = run;
+    }
+    __syncthreads();
+  }
+  tot = wtot[HGS_SCAN_BLOCK / 64 - 1];
+  return ex;
+}
+
+// what a workgroup keeps in LDS per wave for the scan of T
+template <class T> struct hgs_scan_lds { typedef uint32_t type; };
+template <> struct hgs_scan_lds<double> { typedef double type; };
+
 // element i of v[0 .. n) (zero behind the end) scanned over the workgroup: the exclusive prefix; raw = the element, tot =
 // the workgroup's total
 template <class T>
 __device__ __forceinline__ T hgs_scan_block(const T* v, uint32_t i, uint32_t n, T& raw, T& tot) {
-  __shared__ uint32_t wtot[HGS_SCAN_BLOCK / 64];
+  __shared__ typename hgs_scan_lds<T>::type wtot[HGS_SCAN_BLOCK / 64];
   raw = i < n ? v[i] : T();
   return hgs_scan_1k(raw, wtot, tot);
 }

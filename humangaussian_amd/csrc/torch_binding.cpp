@@ -1443,6 +1443,87 @@ std::tuple<Tensor, Tensor> marching_cubes(const Tensor& field, double threshold)
   return {v, t};
 }
 
+// ---- surface samples and the initial Gaussians (include/hgs_rast.h: hgs_surface_*, hgs_init_gaussians) --------------
+// The table of a mesh: (cdf [F + 1] fp64, area, faces of positive area); one host wait, for the 16-byte info block.
+std::tuple<Tensor, double, int64_t> surface_build(const Tensor& vertices, const Tensor& faces) {
+  at::NoGradGuard ng;
+  const c10::Device dev = vertices.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  const auto vf = mesh_inputs(vertices, faces, dev);
+  const Tensor &v = vf.first, &f = vf.second;
+  const int64_t V = v.size(0), F = f.size(0);
+  if (F < 1 || F > HGS_SURFACE_MAX_FACES)
+    throw std::runtime_error("surface_build: 1 .. " + std::to_string(HGS_SURFACE_MAX_FACES) + " faces, got " + std::to_string(F));
+  const auto byte_opts = at::TensorOptions().dtype(at::kByte).device(dev);
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  Tensor cdf = at::empty({F + 1}, byte_opts.dtype(at::kDouble));
+  Tensor scratch = at::empty({(int64_t)hgs_surface_cdf_scratch_bytes((int32_t)F)}, byte_opts);
+  Tensor info_dev = at::empty({(int64_t)sizeof(hgs_surface_info)}, byte_opts);
+  auto* info_ptr = reinterpret_cast<hgs_surface_info*>(info_dev.data_ptr());
+  check_rc(hgs_surface_cdf((int32_t)V, fptr(v), (int32_t)F, f.data_ptr<int32_t>(), cdf.data_ptr<double>(), info_ptr,
+                           scratch.data_ptr(), stream), "hgs_surface_cdf");
+  hgs_surface_info info;
+  if (hipMemcpyAsync(&info, info_ptr, sizeof(info), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    throw std::runtime_error("surface_build: reading the table's info block failed");
+  return {cdf, info.area, (int64_t)info.num_positive};
+}
+
+// (points [N, 3] fp32, face [N] int32 or undefined, uvw [N, 3] fp32 or undefined): one launch, nothing read back
+std::tuple<Tensor, c10::optional<Tensor>, c10::optional<Tensor>> surface_sample(
+    const Tensor& vertices, const Tensor& faces, const Tensor& cdf, int64_t n, uint64_t seed, uint64_t offset, bool want_anchors) {
+  at::NoGradGuard ng;
+  const c10::Device dev = vertices.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  const auto vf = mesh_inputs(vertices, faces, dev);
+  const Tensor &v = vf.first, &f = vf.second;
+  const int64_t V = v.size(0), F = f.size(0);
+  if (n < 0 || n > 0x7fffffffll / 3) throw std::runtime_error("surface_sample: 0 .. 715827882 samples a call");
+  if (cdf.device() != dev || cdf.scalar_type() != at::kDouble || !cdf.is_contiguous() || cdf.numel() != F + 1)
+    throw std::runtime_error("surface_sample: cdf is the (F + 1,) fp64 table surface_build returned for these faces");
+  const auto opts = at::TensorOptions().device(dev).dtype(at::kFloat);
+  Tensor points = at::empty({n, 3}, opts);
+  c10::optional<Tensor> face, uvw;
+  if (want_anchors) { face = at::empty({n}, opts.dtype(at::kInt)); uvw = at::empty({n, 3}, opts); }
+  if (n == 0) return {points, face, uvw};
+  hgs_surface_sample_args a;
+  memset(&a, 0, sizeof(a));
+  a.V = (int32_t)V; a.F = (int32_t)F;
+  a.vertices = fptr(v); a.faces = f.data_ptr<int32_t>(); a.cdf = cdf.data_ptr<double>();
+  a.N = n; a.offset = offset; a.seed = seed;
+  a.points = points.data_ptr<float>();
+  a.face = want_anchors ? face->data_ptr<int32_t>() : nullptr;
+  a.uvw = want_anchors ? uvw->data_ptr<float>() : nullptr;
+  check_rc(hgs_surface_sample(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_surface_sample");
+  return {points, face, uvw};
+}
+
+// create_from_pcd's tensors from distCUDA2's output: [features_dc (P,1,3), features_rest (P,M-1,3), scaling (P,3),
+// rotation (P,4), opacity (P,1), max_radii2D (P)], one launch, nothing read back
+std::vector<Tensor> init_gaussians(const Tensor& dist2, const c10::optional<Tensor>& colors, int64_t M) {
+  at::NoGradGuard ng;
+  const c10::Device dev = dist2.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  if (dist2.dim() != 1) throw std::runtime_error("dist2 must have dimensions (num_points,)");
+  if (M < 1 || M > 4096) throw std::runtime_error("init_gaussians: M = (max_sh_degree + 1)^2 must be in 1 .. 4096");
+  const int64_t P = dist2.size(0);
+  if (colors && (colors->dim() != 2 || colors->size(0) != P || colors->size(1) != 3))
+    throw std::runtime_error("colors must have dimensions (num_points, 3)");
+  DeviceSwitch guard(dev.index());
+  const Tensor d = f32c(dist2, dev, "dist2");
+  Tensor col;
+  if (colors) col = f32c(*colors, dev, "colors");
+  const auto opts = at::TensorOptions().device(dev).dtype(at::kFloat);
+  Tensor dc = at::empty({P, 1, 3}, opts), rest = at::empty({P, M - 1, 3}, opts), scaling = at::empty({P, 3}, opts),
+         rotation = at::empty({P, 4}, opts), opacity = at::empty({P, 1}, opts), radii = at::empty({P}, opts);
+  check_rc(hgs_init_gaussians(P, (int32_t)M, colors ? fptr(col) : nullptr, fptr(d), fptr_mut(dc), fptr_mut(rest),
+                              fptr_mut(scaling), fptr_mut(rotation), fptr_mut(opacity), fptr_mut(radii),
+                              c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_init_gaussians");
+  return {dc, rest, scaling, rotation, opacity, radii};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch binding of libhgs_rast.so (include/hgs_rast.h): autograd node, capacity logic, the one host wait";
   m.def("rasterize", &rasterize, py::call_guard<py::gil_scoped_release>());
@@ -1488,6 +1569,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("field_sample", &field_sample, py::arg("info"), py::arg("axis"), py::arg("plan"), py::arg("lists"), py::arg("points"),
         py::arg("colors") = py::none(), py::arg("normalized") = false, py::call_guard<py::gil_scoped_release>());
   m.def("marching_cubes", &marching_cubes, py::arg("field"), py::arg("threshold"), py::call_guard<py::gil_scoped_release>());
+  m.def("surface_build", &surface_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
+  m.def("surface_sample", &surface_sample, py::arg("vertices"), py::arg("faces"), py::arg("cdf"), py::arg("n"),
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("want_anchors") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("init_gaussians", &init_gaussians, py::arg("dist2"), py::arg("colors") = py::none(), py::arg("M") = 1,
+        py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);
   m.def("abi_version", []() { return hgs_abi_version(); });

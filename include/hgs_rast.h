@@ -796,6 +796,69 @@ typedef struct hgs_fsample_args {
 size_t hgs_fsample_scratch_bytes(int32_t M, int32_t num_blocks);
 int hgs_fsample(const hgs_fsample_args* args, void* stream);
 
+/* ---- area-uniform samples of a triangle mesh (the reference's trimesh.sample.sample_surface, on the device) -------------
+ * This definition is the contract; tests/surface_sample_reference.py restates it in numpy.
+ *
+ * Table (hgs_surface_cdf).  For face f with fp32 vertices a, b, c widened to fp64: e1 = b - a, e2 = c - a, the cross
+ * product component by component (cx = e1y e2z - e1z e2y, cy = e1z e2x - e1x e2z, cz = e1x e2y - e1y e2x),
+ * area = 0.5 * sqrt((cx cx + cy cy) + cz cz), no contraction.  A non-finite area counts as 0; a face with a vertex index
+ * outside [0, V) counts as 0 and its vertices are never read.  cdf [F + 1] fp64: cdf[0] = 0 and cdf[k], k = 1 .. F, the
+ * areas of faces 0 .. k-1 summed in this fixed order: entry k of block b (1024 entries a block) is S_b + (the areas of
+ * the block's entries in front of k, added left to right), S_0 = 0, S_b+1 = S_b + (block b's areas added left to right).
+ * So the table never decreases, a face of area 0 repeats the entry in front of it bit for bit, and the table is the same
+ * from call to call (no floating-point atomics).
+ * A = cdf[F].  info (DEVICE, 16 bytes): A and the number of faces of positive area.  scratch:
+ * hgs_surface_cdf_scratch_bytes(F) bytes.  1 <= F <= HGS_SURFACE_MAX_FACES, V >= 0.  No host wait.
+ *
+ * Samples (hgs_surface_sample, one launch, no host wait).  Sample i of a call has the global index g = offset + i (64 bits,
+ * wrapping); nothing else of the call enters its result, so rows k .. k+m of a call are the rows of a call of m samples at
+ * offset + k.
+ *   words   x0..x3 = Philox4x32-10(counter = (g_lo, g_hi, 0, 0), key = (seed_lo, seed_hi)): multipliers M0 = 0xD2511F53,
+ *           M1 = 0xCD9E8D57; a round: (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); the
+ *           key grows by (0x9E3779B9, 0xBB67AE85) between rounds.
+ *   face    u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53 in fp64, t = u * A, face = the number of k in 1 .. F with
+ *           cdf[k] <= t (clamped to F - 1; t < A, so the clamp never fires).  A face of area 0 is never chosen.
+ *   uvw     k1 = x2 >> 8, k2 = x3 >> 8; if k1 + k2 > 2^24: k1 = 2^24 - k1, k2 = 2^24 - k2 (trimesh's fold);
+ *           uvw = (2^24 - k1 - k2, k1, k2) * 2^-24: exact in fp32, each in [0, 1], their sum exactly 1.
+ *   point   per axis (a u + b v) + c w in fp32, no contraction: the bits of hgs_reanchor with dist = 0.
+ * points [N][3] fp32, face [N] int32, uvw [N][3] fp32: each optional (NULL: not written).  N == 0 launches nothing.
+ * A == 0 (or not > 0): face = -1, uvw = 0 and NaN points for every sample.  cdf is the table hgs_surface_cdf left for
+ * the same vertices and faces.  HGS_EINVAL before any launch for args == NULL, N < 0, V < 0, F outside
+ * 1 .. HGS_SURFACE_MAX_FACES, or a NULL among vertices, faces, cdf.
+ *
+ * hgs_init_gaussians: the tensors GaussianModel.create_from_pcd builds from a cloud, in one launch.  points enter only
+ * through dist2 [P] (hgs_knn_mean_dist2_grid of them); colors [P][3] or NULL (the reference's constant 0.5);
+ * M = (max_sh_degree + 1)^2 >= 1.  Outputs, each optional:
+ *   features_dc [P][1][3] = (c - 0.5f) / 0.28209479177387814f     features_rest [P][M-1][3] = 0
+ *   scaling [P][3] = logf(sqrtf(d < 1e-7f ? 1e-7f : d)), d = dist2 (all three columns; a NaN stays a NaN)
+ *   rotation [P][4] = (1, 0, 0, 0)     opacity [P][1] = the fp32 nearest to ln(0.1f / (1 - 0.1f))     max_radii2D [P] = 0
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_SURFACE_MAX_FACES ((1 << 20) - 1)
+typedef struct hgs_surface_info {
+  double area;                      /* A = cdf[F]                                                                          */
+  uint32_t num_positive;            /* faces of positive area: the ones a sample can fall on                               */
+  uint32_t reserved;
+} hgs_surface_info;
+typedef struct hgs_surface_sample_args {
+  int32_t V, F;
+  const float* vertices;            /* [V][3] */
+  const int32_t* faces;             /* [F][3] */
+  const double* cdf;                /* [F + 1], of hgs_surface_cdf */
+  int64_t N;
+  uint64_t offset;
+  uint64_t seed;
+  float* points;                    /* [N][3] or NULL */
+  int32_t* face;                    /* [N] or NULL */
+  float* uvw;                       /* [N][3] or NULL */
+} hgs_surface_sample_args;
+size_t hgs_surface_cdf_scratch_bytes(int32_t F);
+int hgs_surface_cdf(int32_t V, const float* vertices, int32_t F, const int32_t* faces, double* cdf, hgs_surface_info* info,
+                    void* scratch, void* stream);
+int hgs_surface_sample(const hgs_surface_sample_args* args, void* stream);
+int hgs_init_gaussians(int64_t P, int32_t M, const float* colors, const float* dist2, float* features_dc,
+                       float* features_rest, float* scaling, float* rotation, float* opacity, float* max_radii2D,
+                       void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
