@@ -8,6 +8,7 @@ Only what the rasterize hot path needs:
   view_parallel.py view-parallel multi-GPU rendering (one RCCL all-gather per step)
   step_images.py   guidance_images(): the guidance's two images and the opacity losses of a step
   surface.py       SurfaceSampler / create_from_pcd: the body surface sampled and the initial Gaussians built on the device
+  mesh_view.py     MeshView: the body mesh rasterized forward-only (the animation loop's mesh mode, mesh previews)
   synth.py         synthetic SMPL-X-like clouds + threestudio-style cameras (bench/tests)
 """
 from .rasterizer import (  # noqa: F401

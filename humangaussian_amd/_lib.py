@@ -130,6 +130,27 @@ class HgsSurfaceSampleArgs(Structure):
     ]
 
 
+MESHVIEW_MAX_DIM, MESHVIEW_TILE, MESHVIEW_LIST_BATCH, MESHVIEW_MAX_ATTR = 4096, 16, 256, 8
+
+
+class HgsMeshviewInfo(Structure):
+    """ctypes mirror of `hgs_meshview_info` (the 32 bytes hgs_meshview_plan leaves on the device)."""
+    _fields_ = [("num_refs", ctypes.c_uint64), ("B", c_int32), ("V", c_int32), ("F", c_int32), ("H", c_int32), ("W", c_int32),
+                ("reserved", c_uint32)]
+
+
+class HgsMeshviewArgs(Structure):
+    """ctypes mirror of `hgs_meshview_args` (hgs_meshview_normals / _plan / _draw / _interpolate)."""
+    _fields_ = [
+        ("B", c_int32), ("V", c_int32), ("F", c_int32), ("H", c_int32), ("W", c_int32),
+        ("C", c_int32), ("shade_normals", c_int32), ("background", c_float),
+        ("vertex_stride", c_int64), ("attr_stride", c_int64),
+        ("vertices", c_void_p), ("mvp", c_void_p), ("faces", c_void_p), ("adj_start", c_void_p), ("adj", c_void_p),
+        ("attr", c_void_p), ("rast_in", c_void_p), ("records", c_void_p), ("plan", c_void_p), ("lists", c_void_p),
+        ("info", c_void_p), ("rast", c_void_p), ("image", c_void_p), ("normals", c_void_p),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -214,6 +235,12 @@ EXPORTS = {
     "hgs_surface_cdf": (ctypes.c_int, [c_int32, c_void_p, c_int32] + [c_void_p] * 5),
     "hgs_surface_sample": (ctypes.c_int, [POINTER(HgsSurfaceSampleArgs), c_void_p]),
     "hgs_init_gaussians": (ctypes.c_int, [c_int64, c_int32] + [c_void_p] * 9),
+    "hgs_meshview_plan_bytes": (c_size_t, [c_int32] * 4),
+    "hgs_meshview_normals": (ctypes.c_int, [POINTER(HgsMeshviewArgs), c_void_p]),
+    "hgs_meshview_plan": (ctypes.c_int, [POINTER(HgsMeshviewArgs), c_void_p]),
+    "hgs_meshview_list_bytes": (c_size_t, [POINTER(HgsMeshviewInfo)]),
+    "hgs_meshview_draw": (ctypes.c_int, [POINTER(HgsMeshviewArgs), POINTER(HgsMeshviewInfo), c_void_p]),
+    "hgs_meshview_interpolate": (ctypes.c_int, [POINTER(HgsMeshviewArgs), c_void_p]),
 }
 
 

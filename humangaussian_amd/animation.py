@@ -315,6 +315,20 @@ class AvatarAnimator:
         self.gaussians._xyz = self.anchors.positions(vertices)               # animation.py:384-403, on the device
         return self.renderer.render(camera, antialiasing=self.antialiasing)["image"]      # animation.py:477-482
 
+    @torch.no_grad()
+    def render_mesh_frame(self, vertices, camera) -> torch.Tensor:
+        """The loop's `mesh` mode (animation.py:538-541, `render_mesh_normal` :558-601): the posed mesh shaded with its vertex
+        normals over a white background, (H, W, 3) in [0, 1] on the device, through the camera of `render_frame` - the two
+        views agree pixel for pixel (`mesh_view.mvp_from_camera`).  The `MeshView` of `anchors.faces` is built at the first
+        call."""
+        from .mesh_view import MeshView, mvp_from_camera
+        v = torch.as_tensor(vertices).to(self.anchors.faces.device, torch.float32)
+        view = getattr(self, "_mesh_view", None)
+        if view is None or view.num_vertices != v.shape[-2]:
+            view = self._mesh_view = MeshView(self.anchors.faces, v.shape[-2], device=self.anchors.faces.device)
+        mvp = mvp_from_camera(camera).to(v.device)
+        return view.render_normals(v, mvp, int(camera.image_height), int(camera.image_width))[0]
+
 
 def orbit_frame_camera(i: int, H: int, W: int, radius: float = 2.0, fovy_deg: float = 50.0, device="cuda"):
     """Camera of frame i as the reference's save loop sets it: elevation 0, azimuth i mod 360, radius 2, fovy 50

@@ -31,6 +31,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "pose.hip"
 #include "step_images.hip"
 #include "surface.hip"
+#include "meshview.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -1543,6 +1544,146 @@ int hgs_init_gaussians(int64_t P, int32_t M, const float* colors, const float* d
   if ((n + 255) / 256 > 0x7fffffffll) return HGS_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(hgs_k_init_gaussians, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+namespace {
+struct MvShape { int tiles_x, tiles_y; uint32_t ntiles, n; };
+// the sizes the mesh view's calls accept (include/hgs_rast.h)
+bool mv_shape(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, MvShape& s) {
+  if (B < 0 || B > 65535 || V < 0 || F < 0 || F > (1 << 24) - 1) return false;
+  if (H < 1 || H > HGS_MESHVIEW_MAX_DIM || W < 1 || W > HGS_MESHVIEW_MAX_DIM) return false;
+  s.tiles_x = (W + HGS_MESHVIEW_TILE - 1) / HGS_MESHVIEW_TILE;
+  s.tiles_y = (H + HGS_MESHVIEW_TILE - 1) / HGS_MESHVIEW_TILE;
+  s.ntiles = (uint32_t)(s.tiles_x * s.tiles_y);
+  const long long lim = 0x7fffffffll;
+  if ((long long)B * V >= lim || (long long)B * F >= lim || (long long)B * s.ntiles >= lim) return false;
+  s.n = (uint32_t)B * s.ntiles;
+  return true;
+}
+struct MvCarve { size_t tribox, start, cursor, bsum, total; };
+MvCarve carve_mv(int32_t B, int32_t F, const MvShape& s) {
+  MvCarve c;
+  Carver cv;
+  c.tribox = cv.take((size_t)B * F * 4);
+  c.start = cv.take(((size_t)s.n + 1) * 4);
+  c.cursor = cv.take((size_t)s.n * 4);
+  c.bsum = cv.take(scan_shape((size_t)s.n + 1, 4).bsum_bytes);
+  c.total = cv.off;
+  return c;
+}
+MvPlanPtrs mv_ptrs(const MvCarve& c, void* plan) {
+  char* b = static_cast<char*>(plan);
+  return {reinterpret_cast<uint32_t*>(b + c.tribox), reinterpret_cast<uint32_t*>(b + c.start),
+          reinterpret_cast<uint32_t*>(b + c.cursor), reinterpret_cast<uint32_t*>(b + c.bsum)};
+}
+bool mv_strides_ok(const hgs_meshview_args& a) {
+  return a.vertex_stride == 0 || a.vertex_stride == 3ll * a.V;
+}
+bool mv_attr_ok(const hgs_meshview_args& a) {
+  if (a.C < 1 || a.C > HGS_MESHVIEW_MAX_ATTR || !a.attr) return false;
+  if (a.attr_stride != 0 && a.attr_stride != (long long)a.V * a.C) return false;
+  return !a.shade_normals || a.C == 3;
+}
+}  // namespace
+
+size_t hgs_meshview_plan_bytes(int32_t B, int32_t F, int32_t H, int32_t W) {
+  MvShape s;
+  if (!mv_shape(B, 0, F, H, W, s)) return 0;
+  return carve_mv(B, F, s).total;
+}
+
+// One launch (meshview.hip): a thread per (mesh, vertex).
+int hgs_meshview_normals(const hgs_meshview_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_meshview_args& a = *args;
+  MvShape s;
+  if (!mv_shape(a.B, a.V, a.F, 1, 1, s) || !mv_strides_ok(a)) return HGS_EINVAL;
+  const int Bv = a.vertex_stride ? a.B : 1;
+  if (a.B == 0 || a.V == 0) return HGS_OK;
+  if (!a.vertices || !a.normals || !a.adj_start || (a.F > 0 && (!a.faces || !a.adj))) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const long long n = (long long)Bv * a.V;
+  hipLaunchKernelGGL(hgs_k_mv_normals, dim3((unsigned)((n + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
+                     stream, a, Bv);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+// Two memsets and five launches: vertex records, the triangles' tile boxes and the tiles' counts, the scan.
+int hgs_meshview_plan(const hgs_meshview_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_meshview_args& a = *args;
+  MvShape s;
+  if (!mv_shape(a.B, a.V, a.F, a.H, a.W, s) || !mv_strides_ok(a)) return HGS_EINVAL;
+  if (a.B == 0) return HGS_OK;
+  if (!a.mvp || !a.plan || !a.info || (a.V > 0 && (!a.vertices || !a.records)) || (a.F > 0 && !a.faces)) return HGS_EINVAL;
+  if (((uintptr_t)a.records & 15) || ((uintptr_t)a.plan & 15) || ((uintptr_t)a.info & 7)) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MvCarve c = carve_mv(a.B, a.F, s);
+  const MvPlanPtrs pp = mv_ptrs(c, a.plan);
+  hipError_t e = hipMemsetAsync(a.info, 0, sizeof(hgs_meshview_info), stream);
+  if (e == hipSuccess) e = hipMemsetAsync(pp.start, 0, ((size_t)s.n + 1) * 4, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  const long long nv = (long long)a.B * a.V, nf = (long long)a.B * a.F;
+  if (nv > 0)
+    hipLaunchKernelGGL(hgs_k_mv_vertex, dim3((unsigned)((nv + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
+                       stream, a);
+  if (nf > 0)
+    hipLaunchKernelGGL(hgs_k_mv_count, dim3((unsigned)((nf + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
+                       stream, a, pp, s.tiles_x, s.ntiles);
+  const unsigned gs = scan_shape(s.n, 4).blocks;
+  hipLaunchKernelGGL(hgs_k_mv_scan1, dim3(gs), dim3(1024), 0, stream, pp, s.n);
+  hipLaunchKernelGGL(hgs_k_mv_scan2, dim3(1), dim3(1024), 0, stream, pp, s.n);
+  hipLaunchKernelGGL(hgs_k_mv_scan3, dim3(gs), dim3(1024), 0, stream, a, pp, s.n);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+size_t hgs_meshview_list_bytes(const hgs_meshview_info* info_host) {
+  if (!info_host || info_host->num_refs > 0x7fffffffull) return (size_t)-1;
+  return hgs_align_up((size_t)info_host->num_refs * 4, ALIGN);
+}
+
+// Two launches: the tiles' lists, then one workgroup per tile.
+int hgs_meshview_draw(const hgs_meshview_args* args, const hgs_meshview_info* info_host, void* stream_) {
+  if (!args || !info_host) return HGS_EINVAL;
+  const hgs_meshview_args& a = *args;
+  const hgs_meshview_info& in = *info_host;
+  MvShape s;
+  if (!mv_shape(a.B, a.V, a.F, a.H, a.W, s)) return HGS_EINVAL;
+  if (a.B == 0) return HGS_OK;
+  if (in.B != a.B || in.V != a.V || in.F != a.F || in.H != a.H || in.W != a.W || in.num_refs > 0x7fffffffull) return HGS_EINVAL;
+  if (!a.plan || (!a.rast && !a.image) || (in.num_refs > 0 && (!a.lists || !a.records || !a.faces))) return HGS_EINVAL;
+  if (a.image && !mv_attr_ok(a)) return HGS_EINVAL;
+  if (((uintptr_t)a.records & 15) || ((uintptr_t)a.plan & 15) || ((uintptr_t)a.rast & 15)) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MvPlanPtrs pp = mv_ptrs(carve_mv(a.B, a.F, s), a.plan);
+  const uint32_t nrefs = (uint32_t)in.num_refs;
+  const long long nf = (long long)a.B * a.F;
+  if (nrefs > 0)
+    hipLaunchKernelGGL(hgs_k_mv_fill, dim3((unsigned)((nf + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
+                       stream, a, pp, s.tiles_x, s.ntiles, nrefs);
+  hipLaunchKernelGGL(hgs_k_mv_draw, dim3(s.ntiles, (unsigned)a.B), dim3(HGS_MV_THREADS), 0, stream, a, pp, s.tiles_x, s.ntiles,
+                     nrefs);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshview_interpolate(const hgs_meshview_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_meshview_args& a = *args;
+  MvShape s;
+  if (!mv_shape(a.B, a.V, a.F, a.H, a.W, s)) return HGS_EINVAL;
+  if (a.B == 0) return HGS_OK;
+  if (!a.rast_in || !a.image || ((uintptr_t)a.rast_in & 15) || (a.F > 0 && !a.faces)) return HGS_EINVAL;
+  if (a.C < 1 || a.C > HGS_MESHVIEW_MAX_ATTR || (a.attr_stride != 0 && a.attr_stride != (long long)a.V * a.C)) return HGS_EINVAL;
+  if (a.F > 0 && a.V > 0 && !a.attr) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const long long n = (long long)a.B * a.H * a.W;
+  hipLaunchKernelGGL(hgs_k_mv_interpolate, dim3((unsigned)((n + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
+                     stream, a);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -1524,6 +1524,146 @@ std::vector<Tensor> init_gaussians(const Tensor& dist2, const c10::optional<Tens
   return {dc, rest, scaling, rotation, opacity, radii};
 }
 
+// ---- mesh view (include/hgs_rast.h: hgs_meshview_*): the body mesh rasterized forward-only on the current stream.
+// vertices (Bv, V, 3) fp32 with Bv = 1 (one mesh for every view) or B, faces (F, 3) int32, mvp (B, 4, 4) fp32; everything
+// contiguous on one device, nothing converted here.
+namespace {
+void mv_mesh_args(hgs_meshview_args& a, const Tensor& vertices, const Tensor& faces, int64_t B, const c10::Device& dev,
+                  const char* who) {
+  need_dev(vertices, dev, at::kFloat, who);
+  need_dev(faces, dev, at::kInt, who);
+  if (vertices.dim() != 3 || vertices.size(2) != 3) throw std::runtime_error(std::string(who) + ": vertices must be (Bv, V, 3)");
+  if (faces.dim() != 2 || faces.size(1) != 3) throw std::runtime_error(std::string(who) + ": faces must be (F, 3)");
+  const int64_t Bv = vertices.size(0), V = vertices.size(1), F = faces.size(0);
+  if (Bv != 1 && Bv != B) throw std::runtime_error(std::string(who) + ": vertices must hold one mesh or one per view");
+  if (B > 65535 || B * V >= 0x7fffffffll || B * F >= 0x7fffffffll || F > (1 << 24) - 1)
+    throw std::runtime_error(std::string(who) + ": too many views, vertices or faces");
+  a.B = (int32_t)B; a.V = (int32_t)V; a.F = (int32_t)F;
+  a.vertex_stride = Bv == 1 ? 0 : 3 * V;
+  a.vertices = fptr(vertices);
+  a.faces = F > 0 ? faces.data_ptr<int32_t>() : nullptr;
+}
+void mv_attr_args(hgs_meshview_args& a, const Tensor& attr, const c10::Device& dev, const char* who) {
+  need_dev(attr, dev, at::kFloat, who);
+  if (attr.dim() != 3 || attr.size(1) != a.V || attr.size(2) < 1 || attr.size(2) > HGS_MESHVIEW_MAX_ATTR)
+    throw std::runtime_error(std::string(who) + ": attr must be (Ba, V, C) with 1 <= C <= " + std::to_string(HGS_MESHVIEW_MAX_ATTR));
+  if (attr.size(0) != 1 && attr.size(0) != a.B) throw std::runtime_error(std::string(who) + ": attr must hold one set or one per view");
+  a.C = (int32_t)attr.size(2);
+  a.attr_stride = attr.size(0) == 1 ? 0 : (int64_t)a.V * a.C;
+  a.attr = fptr(attr);
+}
+}  // namespace
+
+Tensor meshview_normals(const Tensor& vertices, const Tensor& faces, const Tensor& adj_start, const Tensor& adj) {
+  at::NoGradGuard ng;
+  const c10::Device dev = vertices.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  hgs_meshview_args a{};
+  mv_mesh_args(a, vertices, faces, vertices.dim() == 3 ? vertices.size(0) : 1, dev, "meshview_normals");
+  need_dev(adj_start, dev, at::kInt, "meshview_normals: adj_start");
+  need_dev(adj, dev, at::kInt, "meshview_normals: adj");
+  if (adj_start.numel() != (int64_t)a.V + 1 || adj.numel() != 3 * (int64_t)a.F)
+    throw std::runtime_error("meshview_normals: adj_start must be (V + 1,) and adj (3 F,)");
+  a.vertex_stride = 3 * (int64_t)a.V;
+  a.adj_start = adj_start.data_ptr<int32_t>();
+  a.adj = a.F > 0 ? adj.data_ptr<int32_t>() : nullptr;
+  Tensor normals = at::empty({(int64_t)a.B, (int64_t)a.V, 3}, vertices.options());
+  a.normals = fptr_mut(normals);
+  check_rc(hgs_meshview_normals(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_meshview_normals");
+  return normals;
+}
+
+// (rast (B, H, W, 4) or None, image (B, H, W, C) or None, records (B, V, 4) int32).  attr None: rast alone.  attr (Ba, V, C):
+// the image, shaded in the draw kernel, and rast too if want_rast.  One host wait (the plan's header sizes the lists).
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>, Tensor> meshview_draw(
+    const Tensor& vertices, const Tensor& mvp, const Tensor& faces, int64_t H, int64_t W, const c10::optional<Tensor>& attr,
+    bool shade_normals, double background, bool want_rast) {
+  at::NoGradGuard ng;
+  const c10::Device dev = mvp.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(mvp, dev, at::kFloat, "meshview_draw: mvp");
+  if (mvp.dim() != 3 || mvp.size(1) != 4 || mvp.size(2) != 4) throw std::runtime_error("meshview_draw: mvp must be (B, 4, 4)");
+  if (H < 1 || H > HGS_MESHVIEW_MAX_DIM || W < 1 || W > HGS_MESHVIEW_MAX_DIM)
+    throw std::runtime_error("meshview_draw: H and W must be in [1, " + std::to_string(HGS_MESHVIEW_MAX_DIM) + "]");
+  const int64_t B = mvp.size(0);
+  hgs_meshview_args a{};
+  mv_mesh_args(a, vertices, faces, B, dev, "meshview_draw");
+  a.H = (int32_t)H; a.W = (int32_t)W;
+  a.mvp = fptr(mvp);
+  const bool shaded = attr.has_value() && attr->defined();
+  if (shaded) {
+    mv_attr_args(a, *attr, dev, "meshview_draw");
+    if (shade_normals && a.C != 3) throw std::runtime_error("meshview_draw: normals have three channels");
+    a.shade_normals = shade_normals ? 1 : 0;
+    a.background = (float)background;
+  }
+  const auto opts = mvp.options();
+  const int64_t V = a.V, C = a.C;
+  Tensor records = at::empty({B, V, 4}, opts.dtype(at::kInt));
+  c10::optional<Tensor> rast, image;
+  const size_t plan_bytes = hgs_meshview_plan_bytes(a.B, a.F, a.H, a.W);
+  if (plan_bytes == 0) throw std::runtime_error("meshview_draw: the sizes are outside the library's limits");
+  hgs_meshview_info info{};
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  Tensor plan, info_dev, lists;
+  if (B > 0) {
+    plan = at::empty({(int64_t)plan_bytes}, opts.dtype(at::kByte));
+    info_dev = at::empty({(int64_t)sizeof(hgs_meshview_info)}, opts.dtype(at::kByte));
+    a.records = V > 0 ? records.data_ptr<int32_t>() : nullptr;
+    a.plan = plan.data_ptr();
+    a.info = reinterpret_cast<hgs_meshview_info*>(info_dev.data_ptr());
+    check_rc(hgs_meshview_plan(&a, stream), "hgs_meshview_plan");
+    if (hipMemcpyAsync(&info, a.info, sizeof(info), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+      throw std::runtime_error("meshview_draw: reading the plan failed");
+  }
+  if (B == 0 || info.num_refs == 0) {            // nothing is listed: the background, without a draw
+    if (!shaded || want_rast) rast = at::zeros({B, H, W, 4}, opts);
+    if (shaded) image = at::full({B, H, W, C}, background, opts);
+    return {rast, image, records};
+  }
+  const size_t bytes = hgs_meshview_list_bytes(&info);
+  if (bytes == (size_t)-1)
+    throw std::runtime_error("meshview_draw: " + std::to_string(info.num_refs) + " (triangle, tile) list entries; at most 2^31 - 1");
+  lists = at::empty({(int64_t)bytes}, opts.dtype(at::kByte));
+  a.lists = lists.data_ptr();
+  if (!shaded || want_rast) { rast = at::empty({B, H, W, 4}, opts); a.rast = rast->data_ptr<float>(); }
+  if (shaded) { image = at::empty({B, H, W, C}, opts); a.image = image->data_ptr<float>(); }
+  check_rc(hgs_meshview_draw(&a, &info, stream), "hgs_meshview_draw");
+  return {rast, image, records};
+}
+
+// attr (Ba, V, C), rast (B, H, W, 4), faces (F, 3) -> (B, H, W, C)
+Tensor meshview_interpolate(const Tensor& attr, const Tensor& rast, const Tensor& faces) {
+  at::NoGradGuard ng;
+  const c10::Device dev = rast.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(rast, dev, at::kFloat, "meshview_interpolate: rast");
+  need_dev(faces, dev, at::kInt, "meshview_interpolate: faces");
+  if (rast.dim() != 4 || rast.size(3) != 4) throw std::runtime_error("meshview_interpolate: rast must be (B, H, W, 4)");
+  if (faces.dim() != 2 || faces.size(1) != 3) throw std::runtime_error("meshview_interpolate: faces must be (F, 3)");
+  const int64_t B = rast.size(0), H = rast.size(1), W = rast.size(2), F = faces.size(0);
+  if (H < 1 || H > HGS_MESHVIEW_MAX_DIM || W < 1 || W > HGS_MESHVIEW_MAX_DIM)
+    throw std::runtime_error("meshview_interpolate: H and W must be in [1, " + std::to_string(HGS_MESHVIEW_MAX_DIM) + "]");
+  if (attr.dim() != 3) throw std::runtime_error("meshview_interpolate: attr must be (Ba, V, C)");
+  const int64_t V = attr.size(1);
+  if (B > 65535 || B * V >= 0x7fffffffll || B * F >= 0x7fffffffll || F > (1 << 24) - 1)
+    throw std::runtime_error("meshview_interpolate: too many views, vertices or faces");
+  hgs_meshview_args a{};
+  a.B = (int32_t)B; a.V = (int32_t)V; a.F = (int32_t)F; a.H = (int32_t)H; a.W = (int32_t)W;
+  mv_attr_args(a, attr, dev, "meshview_interpolate");
+  a.faces = F > 0 ? faces.data_ptr<int32_t>() : nullptr;
+  a.rast_in = fptr(rast);
+  Tensor image = at::empty({B, H, W, (int64_t)a.C}, rast.options());
+  a.image = fptr_mut(image);
+  if (B > 0 && (V == 0 || F == 0)) return image.zero_();
+  check_rc(hgs_meshview_interpolate(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_meshview_interpolate");
+  return image;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch binding of libhgs_rast.so (include/hgs_rast.h): autograd node, capacity logic, the one host wait";
   m.def("rasterize", &rasterize, py::call_guard<py::gil_scoped_release>());
@@ -1573,6 +1713,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("surface_sample", &surface_sample, py::arg("vertices"), py::arg("faces"), py::arg("cdf"), py::arg("n"),
         py::arg("seed") = 0, py::arg("offset") = 0, py::arg("want_anchors") = false, py::call_guard<py::gil_scoped_release>());
   m.def("init_gaussians", &init_gaussians, py::arg("dist2"), py::arg("colors") = py::none(), py::arg("M") = 1,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("meshview_normals", &meshview_normals, py::arg("vertices"), py::arg("faces"), py::arg("adj_start"), py::arg("adj"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("meshview_draw", &meshview_draw, py::arg("vertices"), py::arg("mvp"), py::arg("faces"), py::arg("H"), py::arg("W"),
+        py::arg("attr") = py::none(), py::arg("shade_normals") = false, py::arg("background") = 0.0,
+        py::arg("want_rast") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("meshview_interpolate", &meshview_interpolate, py::arg("attr"), py::arg("rast"), py::arg("faces"),
         py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);

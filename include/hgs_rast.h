@@ -859,6 +859,93 @@ int hgs_init_gaussians(int64_t P, int32_t M, const float* colors, const float* d
                        float* features_rest, float* scaling, float* rotation, float* opacity, float* max_radii2D,
                        void* stream);
 
+/* ---- mesh view: a forward triangle rasterizer for the body mesh (the reference's render_mesh_normal) ------------------
+ * The reference's animation loop draws the posed SMPL-X mesh shaded with its vertex normals through nvdiffrast's rasterize
+ * and interpolate (animation.py:558-601).  These entry points are the forward-only subset that needs: no autograd, no
+ * antialias, no textures.  All arithmetic is fp32 with every operation rounded once (no contraction; 1 / x, a / b and sqrt
+ * are the correctly rounded IEEE operations) or exact integer arithmetic, so a call is bit-reproducible and view b of a
+ * batch has the bits of a call with it alone.  Float atomics are not used; integer atomics only count and hand out slots.
+ * vertices [V][3] (vertex_stride = 0: one mesh for all views) or [B][V][3] (vertex_stride = 3 V), mvp [B][4][4] row-major,
+ * faces [F][3] int32 (a face with an index outside [0, V) is dropped).
+ * 1. Vertex stage, per (view, vertex), m = mvp[b]:  c_i = ((m[i][0] x + m[i][1] y) + m[i][2] z) + m[i][3];  invw = 1 / c_3;
+ *    xs = ((c_0 invw) 0.5 + 0.5) (float)(W << 8), ys likewise with c_1 and H;  zw = c_2 invw;  x_fix = (int)rintf(xs) (8
+ *    sub-pixel bits).  The vertex is VALID iff c_3 > 0, xs, ys and zw are finite and |xs|, |ys| < 2^23.  records[b][v] =
+ *    {x_fix, y_fix, bits(zw), bits(invw)}, or {INT32_MIN, 0, 0, 0} for an invalid vertex.  Pixel (row r, column c) is sampled
+ *    at (c 256 + 128, r 256 + 128); row 0 is y_ndc = -1 (nvdiffrast's convention, and the 3DGS camera's).
+ * 2. Coverage, exact in int64 (|coordinate| <= 2^23: differences < 2^25, cross products < 2^51).  With u x v = u_x v_y - u_y v_x
+ *    and a, b, c the fixed-point corners: area2 = (b - a) x (c - a).  A triangle with an invalid vertex or area2 == 0 is
+ *    dropped; both windings are drawn.  s = sign(area2), A = s area2, E0 = s ((c - b) x (p - b)), E1 = s ((a - c) x (p - c)),
+ *    E2 = A - E0 - E1.  The sample p is inside iff for every i: E_i > 0, or E_i == 0 and edge i owns its boundary: with
+ *    d0 = s (c - b), d1 = s (a - c), d2 = s (b - a), edge i owns iff d_y > 0 or (d_y == 0 and d_x > 0).  A sample exactly on
+ *    an edge two triangles share belongs to exactly one of them (with rows growing with y: a horizontal edge belongs to
+ *    the triangle below it, any other edge to the triangle on its left - a quad on pixel centres owns its top row and its
+ *    right column).  There is NO near-plane clipping: a triangle with a vertex at c_3 <= 0 is dropped (a difference from
+ *    nvdiffrast).
+ * 3. Fragment:  ia = 1 / (float)A,  b_i = (float)E_i ia (int64 -> fp32 rounds to nearest even);  z = (b0 zw_a + b1 zw_b) +
+ *    b2 zw_c; the fragment is discarded unless -1 <= z <= 1.  A pixel's winner has the smallest z, ties go to the lower
+ *    face index - whatever the order of the internal lists.  p_i = b_i invw_i, d = (p0 + p1) + p2, u = p0 / d, v = p1 / d
+ *    (perspective-correct weights of corners 0 and 1, as nvdiffrast's).  rast[b][r][c] = {u, v, z, (float)(face + 1)};
+ *    a pixel nothing covers is all zeros.
+ * 4. Interpolate, C <= HGS_MESHVIEW_MAX_ATTR channels of attr [V][C] (attr_stride = 0) or [B][V][C] (attr_stride = V C):
+ *    ((u a0) + (v a1)) + (((1 - u) - v) a2) with a_k the attribute at corner k of the face; zeros where the fourth component
+ *    of rast is not a face index in [1, F].
+ * 5. Vertex normals (animation.py:573-590): adj_start [V + 1], adj [adj_start[V]] is the vertex -> corner adjacency in CSR
+ *    form, each entry 3 face + corner, ascending inside a vertex.  n = the sum, in that order, component by component, of
+ *    cross(v1 - v0, v2 - v0) = (e1_y e2_z - e1_z e2_y, e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x) of the entries' faces (a
+ *    gather: no atomics).  SAFE NORMALISE: dot = (n_x n_x + n_y n_y) + n_z n_z; (0, 0, 1) if dot <= 1e-20f (or NaN), else
+ *    n / sqrtf(fmaxf(dot, 1e-20f)) component by component.
+ * 6. shade_normals != 0 (render_mesh_normal; C must be 3): the interpolated value gets the same safe normalise, then
+ *    (n + 1) 0.5.  In an image, pixels without a face are `background` in every channel.
+ * Calls: hgs_meshview_normals writes normals [Bv][V][3] for the Bv = (vertex_stride ? B : 1) meshes.  hgs_meshview_plan
+ * writes records and, into plan (hgs_meshview_plan_bytes(B, F, H, W) bytes), every triangle's box of 16 x 16 pixel tiles,
+ * the tiles' counts and their exclusive scan (gridscan.h); *info (DEVICE, 32 bytes) receives the sizes and the number of
+ * list entries.  The caller copies *info to the host - the one host read of a call, as the field and mesh index builders
+ * have one - and allocates hgs_meshview_list_bytes(info_host) bytes (0 is valid: nothing is listed).  hgs_meshview_draw
+ * fills the tiles' lists (it uses up the plan's cursors: one draw per plan) and draws, one workgroup per tile: with image == NULL it writes rast [B][H][W][4]; else image
+ * [B][H][W][C] shaded from attr directly (rast may be NULL: no round trip) and rast as well if it is given.
+ * hgs_meshview_interpolate reads rast_in [B][H][W][4] and writes image (zeros for pixels without a face; background is not
+ * applied).  Limits: B in [0, 65535], H and W in [1, 4096], B V, B F and B tiles below 2^31, at most 2^31 - 1 list entries
+ * (hgs_meshview_list_bytes returns (size_t)-1 beyond).  B == 0, or F == 0 for normals: HGS_OK without a launch.
+ * Returns HGS_EINVAL for sizes outside these or a NULL pointer of an array that has elements.
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_MESHVIEW_MAX_DIM 4096
+#define HGS_MESHVIEW_TILE 16          /* pixels per tile edge: 256 threads, one pixel each */
+#define HGS_MESHVIEW_LIST_BATCH 256   /* triangles of a tile's list staged through LDS at a time */
+#define HGS_MESHVIEW_MAX_ATTR 8
+typedef struct hgs_meshview_info {
+  uint64_t num_refs;                /* (triangle, tile) list entries of the call */
+  int32_t B, V, F, H, W;
+  uint32_t reserved;
+} hgs_meshview_info;
+typedef struct hgs_meshview_args {
+  int32_t B, V, F, H, W;
+  int32_t C;                        /* attribute channels, 1..HGS_MESHVIEW_MAX_ATTR (draw with image, interpolate) */
+  int32_t shade_normals;
+  float background;
+  int64_t vertex_stride;            /* floats between the views' meshes: 0 or 3 V */
+  int64_t attr_stride;              /* floats between the views' attributes: 0 or V C */
+  const float* vertices;
+  const float* mvp;
+  const int32_t* faces;
+  const int32_t* adj_start;         /* normals */
+  const int32_t* adj;
+  const float* attr;
+  const float* rast_in;             /* interpolate */
+  int32_t* records;                 /* [B][V][4]: written by plan, read by draw */
+  void* plan;
+  void* lists;
+  hgs_meshview_info* info;          /* DEVICE: written by plan */
+  float* rast;
+  float* image;
+  float* normals;
+} hgs_meshview_args;
+size_t hgs_meshview_plan_bytes(int32_t B, int32_t F, int32_t H, int32_t W);   /* 0 for sizes the calls refuse */
+int hgs_meshview_normals(const hgs_meshview_args* args, void* stream);
+int hgs_meshview_plan(const hgs_meshview_args* args, void* stream);
+size_t hgs_meshview_list_bytes(const hgs_meshview_info* info_host);
+int hgs_meshview_draw(const hgs_meshview_args* args, const hgs_meshview_info* info_host, void* stream);
+int hgs_meshview_interpolate(const hgs_meshview_args* args, void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
