@@ -9,6 +9,7 @@ Only what the rasterize hot path needs:
   step_images.py   guidance_images(): the guidance's two images and the opacity losses of a step
   surface.py       SurfaceSampler / create_from_pcd: the body surface sampled and the initial Gaussians built on the device
   mesh_view.py     MeshView: the body mesh rasterized forward-only (the animation loop's mesh mode, mesh previews)
+  meshclean.py     mesh_components / clean_mesh / decimate_mesh: the extracted mesh without floaters, decimated to a face budget
   synth.py         synthetic SMPL-X-like clouds + threestudio-style cameras (bench/tests)
 """
 from .rasterizer import (  # noqa: F401
@@ -18,6 +19,7 @@ from .rasterizer import (  # noqa: F401
     rasterize_gaussians_batch,
 )
 
+from .meshclean import clean_mesh, decimate_mesh, mesh_components  # noqa: F401
 from .step_images import StepImages, guidance_images  # noqa: F401
 from .surface import (  # noqa: F401
     SurfaceSampler,
@@ -29,4 +31,4 @@ from .surface import (  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
            "rasterize_gaussians_batch", "StepImages", "guidance_images", "SurfaceSampler", "sample_surface",
-           "create_from_points", "create_from_pcd", "init_from_body"]
+           "create_from_points", "create_from_pcd", "init_from_body", "mesh_components", "clean_mesh", "decimate_mesh"]

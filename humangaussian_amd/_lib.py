@@ -151,6 +151,25 @@ class HgsMeshviewArgs(Structure):
     ]
 
 
+MESHCLEAN_G_MAX, MESHCLEAN_MAX_ITEMS = 1024, 1 << 29
+
+
+class HgsMeshcleanInfo(Structure):
+    """ctypes mirror of `hgs_meshclean_info` (the 64 bytes the hgs_meshclean_* calls keep on the device)."""
+    _fields_ = [("bmin", c_uint32 * 3), ("bmax", c_uint32 * 3), ("bad_faces", c_uint32), ("error", c_uint32),
+                ("num_vertices", c_uint32), ("num_faces", c_uint32), ("reserved", c_uint32 * 6)]
+
+
+class HgsMeshcleanArgs(Structure):
+    """ctypes mirror of `hgs_meshclean_args` (every hgs_meshclean_* call)."""
+    _fields_ = [
+        ("V", c_int32), ("F", c_int32), ("vertices", c_void_p), ("faces", c_void_p), ("scratch", c_void_p),
+        ("info", c_void_p), ("labels", c_void_p), ("comp_faces", c_void_p), ("comp_diag2", c_void_p),
+        ("min_f", c_int32), ("min_d", c_float), ("vertices_out", c_void_p), ("faces_out", c_void_p),
+        ("vertex_src", c_void_p),
+    ]
+
+
 class HgsStatus(Structure):
     _fields_ = [
         ("num_rendered", c_uint32), ("active_tiles", c_uint32), ("num_pairs", c_uint32),
@@ -241,6 +260,15 @@ EXPORTS = {
     "hgs_meshview_list_bytes": (c_size_t, [POINTER(HgsMeshviewInfo)]),
     "hgs_meshview_draw": (ctypes.c_int, [POINTER(HgsMeshviewArgs), POINTER(HgsMeshviewInfo), c_void_p]),
     "hgs_meshview_interpolate": (ctypes.c_int, [POINTER(HgsMeshviewArgs), c_void_p]),
+    "hgs_meshclean_scratch_bytes": (c_size_t, [c_int32, c_int32]),
+    "hgs_meshclean_begin": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), c_void_p]),
+    "hgs_meshclean_rounds": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), c_int32, c_void_p, c_void_p]),
+    "hgs_meshclean_components": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), c_void_p]),
+    "hgs_meshclean_clean_mark": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), c_void_p]),
+    "hgs_meshclean_clean_emit": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), POINTER(HgsMeshcleanInfo), c_void_p]),
+    "hgs_meshclean_count": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), POINTER(c_int32), c_void_p, c_void_p]),
+    "hgs_meshclean_decimate_mark": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), c_int32, c_void_p]),
+    "hgs_meshclean_decimate_emit": (ctypes.c_int, [POINTER(HgsMeshcleanArgs), POINTER(HgsMeshcleanInfo), c_void_p]),
 }
 
 

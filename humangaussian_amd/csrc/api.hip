@@ -32,6 +32,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "step_images.hip"
 #include "surface.hip"
 #include "meshview.hip"
+#include "meshclean.hip"
 
 // render_bwd.hip is a separate translation unit (different optimisation flags)
 extern "C" __global__ void hgs_k_render_bwd(View, Layout, const hgs_status*, const SortRec*, const float*,
@@ -1684,6 +1685,221 @@ int hgs_meshview_interpolate(const hgs_meshview_args* args, void* stream_) {
   const long long n = (long long)a.B * a.H * a.W;
   hipLaunchKernelGGL(hgs_k_mv_interpolate, dim3((unsigned)((n + HGS_MV_THREADS - 1) / HGS_MV_THREADS)), dim3(HGS_MV_THREADS), 0,
                      stream, a);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+
+namespace {
+// one scratch buffer for every hgs_meshclean_* call of a mesh
+struct MclCarve {
+  size_t cbox, vert_keep, face_keep, vert_src, face_src, new_of_old, bsum_v, bsum_f, cell_of, rep, sums, cnt, table_v,
+      table_f, total;
+  uint32_t cap_v, cap_f;
+};
+// capacity of a hash table of n items: the power of two in [2 n, 4 n), at least 64
+uint32_t mcl_capacity(size_t n) {
+  uint32_t c = 64;
+  while ((size_t)c < 2 * n) c <<= 1;
+  return c;
+}
+bool mcl_sizes_ok(int32_t V, int32_t F) { return V >= 0 && F >= 0 && V <= HGS_MESHCLEAN_MAX_ITEMS && F <= HGS_MESHCLEAN_MAX_ITEMS; }
+MclCarve carve_mcl(int32_t V, int32_t F) {
+  MclCarve c;
+  const size_t v = (size_t)V, f = (size_t)F;
+  c.cap_v = mcl_capacity(v);
+  c.cap_f = mcl_capacity(f);
+  Carver cv;
+  c.cbox = cv.take(v * 32);
+  c.vert_keep = cv.take(v);
+  c.face_keep = cv.take(f);
+  c.vert_src = cv.take(v * 4);
+  c.face_src = cv.take(f * 4);
+  c.new_of_old = cv.take(v * 4);
+  c.bsum_v = cv.take(scan_shape(v, 4).bsum_bytes);
+  c.bsum_f = cv.take(scan_shape(f, 4).bsum_bytes);
+  c.cell_of = cv.take(v * 4);
+  c.rep = cv.take(v * 4);
+  c.sums = cv.take(v * 24);
+  c.cnt = cv.take(v * 4);
+  c.table_v = cv.take((size_t)c.cap_v * 4);
+  c.table_f = cv.take((size_t)c.cap_f * 4);
+  c.total = cv.off;
+  return c;
+}
+extern "C++" {
+template <class T> T* mcl_at(void* scratch, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(scratch) + off); }
+}
+unsigned mcl_blocks(int32_t n) { return (unsigned)((n + 255) / 256); }
+bool mcl_args_ok(const hgs_meshclean_args* a) {
+  return a && mcl_sizes_ok(a->V, a->F) && a->info && (a->V == 0 || a->vertices) && (a->F == 0 || a->faces);
+}
+// keep[n] -> src[0 .. *num) = the kept indices in ascending order (hgs_compact_index's three launches)
+void mcl_compact(int32_t n, const uint8_t* keep, int32_t* src, uint32_t* num, uint32_t* bsum, hipStream_t stream) {
+  const int nb = (int)scan_shape((size_t)n, 4).blocks;
+  hipLaunchKernelGGL(hgs_k_keep_count, dim3(nb), dim3(1024), 0, stream, (int)n, keep, bsum);
+  hipLaunchKernelGGL(hgs_k_keep_scan, dim3(1), dim3(1024), 0, stream, nb, bsum, num);
+  hipLaunchKernelGGL(hgs_k_keep_index, dim3(nb), dim3(1024), 0, stream, (int)n, keep, bsum, src);
+}
+bool mcl_info_ok(const hgs_meshclean_args& a, const hgs_meshclean_info* in) {
+  return in && in->error == 0 && in->bad_faces == 0 && in->num_vertices <= (uint32_t)a.V && in->num_faces <= (uint32_t)a.F;
+}
+}  // namespace
+
+size_t hgs_meshclean_scratch_bytes(int32_t V, int32_t F) { return mcl_sizes_ok(V, F) ? carve_mcl(V, F).total : 0; }
+
+int hgs_meshclean_begin(const hgs_meshclean_args* args, void* stream_) {
+  if (!mcl_args_ok(args)) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hipError_t e = box_init(a.info, sizeof(hgs_meshclean_info), a.info->bmin, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  if (a.V > 0) hipLaunchKernelGGL(hgs_k_mcl_init, dim3(mcl_blocks(a.V)), dim3(256), 0, stream, (int)a.V, a.vertices, a.labels, a.info);
+  if (a.F > 0) hipLaunchKernelGGL(hgs_k_mcl_bad_faces, dim3(mcl_blocks(a.F)), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, a.info);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_rounds(const hgs_meshclean_args* args, int32_t rounds, uint32_t* changed, void* stream_) {
+  if (!mcl_args_ok(args) || rounds < 1 || rounds > 64 || !changed) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  if (a.V > 0 && !a.labels) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const hipError_t e = hipMemsetAsync(changed, 0, (size_t)rounds * 4, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  if (a.V == 0 || a.F == 0) return HGS_OK;
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(hgs_k_mcl_hook, dim3(mcl_blocks(a.F)), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, a.labels, changed + r);
+    hipLaunchKernelGGL(hgs_k_mcl_jump, dim3(mcl_blocks(a.V)), dim3(256), 0, stream, (int)a.V, a.labels, changed + r);
+  }
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_components(const hgs_meshclean_args* args, void* stream_) {
+  if (!mcl_args_ok(args)) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  if (a.V == 0) return HGS_OK;
+  if (!a.labels || !a.comp_faces || !a.comp_diag2 || !a.scratch) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MclCarve c = carve_mcl(a.V, a.F);
+  uint32_t* cbox = mcl_at<uint32_t>(a.scratch, c.cbox);
+  hipLaunchKernelGGL(hgs_k_mcl_comp_clear, dim3(mcl_blocks(a.V)), dim3(256), 0, stream, (int)a.V, cbox, a.comp_faces);
+  hipLaunchKernelGGL(hgs_k_mcl_comp_box, dim3(mcl_blocks(a.V)), dim3(256), 0, stream, (int)a.V, a.vertices, a.labels, cbox);
+  if (a.F > 0)
+    hipLaunchKernelGGL(hgs_k_mcl_comp_faces, dim3(mcl_blocks(a.F)), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, a.labels, a.comp_faces);
+  hipLaunchKernelGGL(hgs_k_mcl_comp_diag, dim3(mcl_blocks(a.V)), dim3(256), 0, stream, (int)a.V, a.labels, cbox, a.comp_diag2);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_clean_mark(const hgs_meshclean_args* args, void* stream_) {
+  if (!mcl_args_ok(args)) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  if (a.V == 0 || a.F == 0) return HGS_OK;                 // (info->num_* are 0 since hgs_meshclean_begin)
+  if (!a.labels || !a.comp_faces || !a.comp_diag2 || !a.scratch) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MclCarve c = carve_mcl(a.V, a.F);
+  uint8_t* vert_keep = mcl_at<uint8_t>(a.scratch, c.vert_keep);
+  uint8_t* face_keep = mcl_at<uint8_t>(a.scratch, c.face_keep);
+  const hipError_t e = hipMemsetAsync(vert_keep, 0, (size_t)a.V, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  hipLaunchKernelGGL(hgs_k_mcl_clean_mark, dim3(mcl_blocks(a.F)), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, a.labels,
+                     a.comp_faces, a.comp_diag2, a.info, (int)a.min_f, a.min_d, face_keep, vert_keep);
+  mcl_compact(a.V, vert_keep, mcl_at<int32_t>(a.scratch, c.vert_src), &a.info->num_vertices, mcl_at<uint32_t>(a.scratch, c.bsum_v), stream);
+  mcl_compact(a.F, face_keep, mcl_at<int32_t>(a.scratch, c.face_src), &a.info->num_faces, mcl_at<uint32_t>(a.scratch, c.bsum_f), stream);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_clean_emit(const hgs_meshclean_args* args, const hgs_meshclean_info* info_host, void* stream_) {
+  if (!mcl_args_ok(args) || !mcl_info_ok(*args, info_host)) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  const int32_t Vn = (int32_t)info_host->num_vertices, Fn = (int32_t)info_host->num_faces;
+  if (Vn == 0 && Fn == 0) return HGS_OK;
+  if (!a.scratch || (Vn > 0 && !a.vertices_out) || (Fn > 0 && (!a.faces_out || Vn == 0))) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MclCarve c = carve_mcl(a.V, a.F);
+  const int32_t* vert_src = mcl_at<int32_t>(a.scratch, c.vert_src);
+  int32_t* new_of_old = mcl_at<int32_t>(a.scratch, c.new_of_old);
+  const long long nf = 3ll * Vn;
+  hipLaunchKernelGGL(hgs_k_gather_rows, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, nf, 3, vert_src, a.vertices,
+                     a.vertices_out);
+  hipLaunchKernelGGL(hgs_k_mcl_invert, dim3(mcl_blocks(Vn)), dim3(256), 0, stream, (int)Vn, vert_src, new_of_old, a.vertex_src);
+  if (Fn > 0)
+    hipLaunchKernelGGL(hgs_k_mcl_faces_out, dim3((unsigned)((3ll * Fn + 255) / 256)), dim3(256), 0, stream, (int)Fn,
+                       mcl_at<const int32_t>(a.scratch, c.face_src), a.faces, static_cast<const int32_t*>(nullptr), new_of_old,
+                       a.faces_out);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_count(const hgs_meshclean_args* args, const int32_t* g, uint32_t* counts, void* stream_) {
+  if (!mcl_args_ok(args) || !g || !counts) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  MclProbe probe;
+  bool any = false;
+  for (int k = 0; k < 3; ++k) {
+    if (g[k] > HGS_MESHCLEAN_G_MAX) return HGS_EINVAL;
+    probe.g[k] = g[k] < 1 ? 0 : g[k];
+    any = any || probe.g[k] > 0;
+  }
+  if (a.V == 0 || a.F == 0 || !any) return HGS_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_mcl_count, dim3(mcl_blocks(a.F)), dim3(256), 0, stream, (int)a.V, a.vertices, (int)a.F, a.faces,
+                     a.info, probe, counts);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_decimate_mark(const hgs_meshclean_args* args, int32_t g, void* stream_) {
+  if (!mcl_args_ok(args) || g < 1 || g > HGS_MESHCLEAN_G_MAX) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  if (a.V == 0 || a.F == 0) return HGS_OK;
+  if (!a.scratch) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MclCarve c = carve_mcl(a.V, a.F);
+  uint32_t* table_v = mcl_at<uint32_t>(a.scratch, c.table_v);
+  uint32_t* table_f = mcl_at<uint32_t>(a.scratch, c.table_f);
+  uint32_t* cell_of = mcl_at<uint32_t>(a.scratch, c.cell_of);
+  int32_t* rep = mcl_at<int32_t>(a.scratch, c.rep);
+  unsigned long long* sums = mcl_at<unsigned long long>(a.scratch, c.sums);
+  uint32_t* cnt = mcl_at<uint32_t>(a.scratch, c.cnt);
+  uint8_t* rep_used = mcl_at<uint8_t>(a.scratch, c.vert_keep);
+  uint8_t* face_keep = mcl_at<uint8_t>(a.scratch, c.face_keep);
+  hipError_t e = hipMemsetAsync(table_v, 0xff, (size_t)c.cap_v * 4, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(table_f, 0xff, (size_t)c.cap_f * 4, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(sums, 0, (size_t)a.V * 24, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)a.V * 4, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(rep_used, 0, (size_t)a.V, stream);
+  if (e != hipSuccess) return hip_rc(e);
+  const unsigned gv = mcl_blocks(a.V), gf = mcl_blocks(a.F);
+  hipLaunchKernelGGL(hgs_k_mcl_cell_insert, dim3(gv), dim3(256), 0, stream, (int)a.V, a.vertices, a.info, (int)g, c.cap_v, table_v, cell_of);
+  hipLaunchKernelGGL(hgs_k_mcl_cell_lookup, dim3(gv), dim3(256), 0, stream, (int)a.V, a.vertices, a.info, c.cap_v, table_v, cell_of, rep, sums, cnt);
+  hipLaunchKernelGGL(hgs_k_mcl_face_insert, dim3(gf), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, rep, a.info, c.cap_f, table_f);
+  hipLaunchKernelGGL(hgs_k_mcl_face_mark, dim3(gf), dim3(256), 0, stream, (int)a.V, (int)a.F, a.faces, rep, a.info, c.cap_f, table_f, face_keep, rep_used);
+  mcl_compact(a.V, rep_used, mcl_at<int32_t>(a.scratch, c.vert_src), &a.info->num_vertices, mcl_at<uint32_t>(a.scratch, c.bsum_v), stream);
+  mcl_compact(a.F, face_keep, mcl_at<int32_t>(a.scratch, c.face_src), &a.info->num_faces, mcl_at<uint32_t>(a.scratch, c.bsum_f), stream);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+int hgs_meshclean_decimate_emit(const hgs_meshclean_args* args, const hgs_meshclean_info* info_host, void* stream_) {
+  if (!mcl_args_ok(args) || !mcl_info_ok(*args, info_host)) return HGS_EINVAL;
+  const hgs_meshclean_args& a = *args;
+  const int32_t Vn = (int32_t)info_host->num_vertices, Fn = (int32_t)info_host->num_faces;
+  if (Vn == 0 && Fn == 0) return HGS_OK;
+  if (!a.scratch || (Vn > 0 && !a.vertices_out) || (Fn > 0 && (!a.faces_out || Vn == 0))) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const MclCarve c = carve_mcl(a.V, a.F);
+  int32_t* new_of_old = mcl_at<int32_t>(a.scratch, c.new_of_old);
+  hipLaunchKernelGGL(hgs_k_mcl_cell_means, dim3(mcl_blocks(Vn)), dim3(256), 0, stream, (int)Vn,
+                     mcl_at<const int32_t>(a.scratch, c.vert_src), a.info, mcl_at<const unsigned long long>(a.scratch, c.sums),
+                     mcl_at<const uint32_t>(a.scratch, c.cnt), new_of_old, a.vertices_out);
+  if (Fn > 0)
+    hipLaunchKernelGGL(hgs_k_mcl_faces_out, dim3((unsigned)((3ll * Fn + 255) / 256)), dim3(256), 0, stream, (int)Fn,
+                       mcl_at<const int32_t>(a.scratch, c.face_src), a.faces, mcl_at<const int32_t>(a.scratch, c.rep), new_of_old,
+                       a.faces_out);
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

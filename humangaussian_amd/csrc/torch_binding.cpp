@@ -20,7 +20,9 @@
 #include <atomic>
 #include <chrono>
 #include <thread>
+#include <cstring>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <mutex>
 #include <utility>
@@ -1664,6 +1666,172 @@ Tensor meshview_interpolate(const Tensor& attr, const Tensor& rast, const Tensor
   return image;
 }
 
+// ---- mesh cleaning and decimation (include/hgs_rast.h: hgs_meshclean_*) -------------------------------------------------
+namespace {
+constexpr int MCL_ROUNDS_PER_READ = 4;     // component rounds launched between two host reads of their change counters
+
+// one mesh's call state: the checked inputs, the scratch and the device info block
+struct MclCall {
+  c10::Device dev;
+  Tensor v, f, scratch, info_dev, labels, comp_faces, comp_diag2;
+  hgs_meshclean_args a{};
+  hipStream_t stream = nullptr;
+  std::unique_ptr<DeviceSwitch> guard;
+  MclCall(const Tensor& vertices, const Tensor& faces, const char* who) : dev(vertices.device()) {
+    if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+    guard.reset(new DeviceSwitch(dev.index()));
+    if (vertices.dim() != 2 || vertices.size(1) != 3) throw std::runtime_error(std::string(who) + ": vertices must be (V, 3)");
+    if (faces.dim() != 2 || faces.size(1) != 3) throw std::runtime_error(std::string(who) + ": faces must be (F, 3)");
+    need_dev(faces, dev, at::kInt, "faces");
+    if (vertices.size(0) > HGS_MESHCLEAN_MAX_ITEMS || faces.size(0) > HGS_MESHCLEAN_MAX_ITEMS)
+      throw std::runtime_error(std::string(who) + ": at most 2^29 vertices and faces");
+    v = f32c(vertices, dev, "vertices");
+    f = faces.contiguous();
+    a.V = (int32_t)v.size(0);
+    a.F = (int32_t)f.size(0);
+    const auto byte_opts = at::TensorOptions().dtype(at::kByte).device(dev);
+    scratch = at::empty({(int64_t)hgs_meshclean_scratch_bytes(a.V, a.F)}, byte_opts);
+    info_dev = at::empty({(int64_t)sizeof(hgs_meshclean_info)}, byte_opts);
+    a.vertices = fptr(v);
+    a.faces = a.F > 0 ? f.data_ptr<int32_t>() : nullptr;
+    a.scratch = scratch.data_ptr();
+    a.info = reinterpret_cast<hgs_meshclean_info*>(info_dev.data_ptr());
+    stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+  }
+  void read(void* dst, const void* src, size_t bytes, const char* what) {
+    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+      throw std::runtime_error(std::string("humangaussian_amd: reading ") + what + " failed");
+  }
+  hgs_meshclean_info read_info() {
+    hgs_meshclean_info info;
+    read(&info, a.info, sizeof(info), "the mesh info block");
+    if (info.error != 0)
+      throw std::runtime_error("humangaussian_amd: a hash table of the mesh decimation ran into its probe bound (error " +
+                               std::to_string(info.error) + ")");
+    return info;
+  }
+  // labels, comp_faces, comp_diag2 of the mesh; returns {rounds, bad faces}.  One host read per MCL_ROUNDS_PER_READ rounds.
+  std::pair<int64_t, int64_t> components() {
+    const auto opts = at::TensorOptions().device(dev);
+    labels = at::empty({(int64_t)a.V}, opts.dtype(at::kInt));
+    comp_faces = at::empty({(int64_t)a.V}, opts.dtype(at::kInt));
+    comp_diag2 = at::empty({(int64_t)a.V}, opts.dtype(at::kFloat));
+    a.labels = a.V > 0 ? labels.data_ptr<int32_t>() : nullptr;
+    a.comp_faces = a.V > 0 ? comp_faces.data_ptr<int32_t>() : nullptr;
+    a.comp_diag2 = fptr_mut(comp_diag2);
+    check_rc(hgs_meshclean_begin(&a, stream), "hgs_meshclean_begin");
+    Tensor changed_dev = at::empty({MCL_ROUNDS_PER_READ}, opts.dtype(at::kInt));
+    auto* changed_ptr = reinterpret_cast<uint32_t*>(changed_dev.data_ptr());
+    const int64_t cap = (int64_t)a.V + 1 + MCL_ROUNDS_PER_READ;       // V + 1 rounds always suffice
+    int64_t rounds = 0;
+    for (bool settled = false; !settled;) {
+      if (rounds >= cap)
+        throw std::runtime_error("humangaussian_amd: the mesh components did not settle in " + std::to_string(cap) + " rounds");
+      check_rc(hgs_meshclean_rounds(&a, MCL_ROUNDS_PER_READ, changed_ptr, stream), "hgs_meshclean_rounds");
+      uint32_t changed[MCL_ROUNDS_PER_READ];
+      read(changed, changed_ptr, sizeof(changed), "the component rounds' counters");
+      for (int r = 0; r < MCL_ROUNDS_PER_READ && !settled; ++r) {
+        ++rounds;
+        settled = changed[r] == 0;
+      }
+    }
+    check_rc(hgs_meshclean_components(&a, stream), "hgs_meshclean_components");
+    hgs_meshclean_info info;
+    read(&info, a.info, sizeof(info), "the mesh info block");
+    return {rounds, (int64_t)info.bad_faces};
+  }
+  void no_bad_faces(const hgs_meshclean_info& info, const char* who) const {
+    if (info.bad_faces != 0)
+      throw std::runtime_error(std::string(who) + ": " + std::to_string(info.bad_faces) + " faces index vertices outside [0, " +
+                               std::to_string(a.V) + ")");
+  }
+  // the output tensors of an emit call
+  std::pair<Tensor, Tensor> outputs(const hgs_meshclean_info& info) {
+    const auto opts = at::TensorOptions().device(dev);
+    Tensor vo = at::empty({(int64_t)info.num_vertices, 3}, opts.dtype(at::kFloat));
+    Tensor fo = at::empty({(int64_t)info.num_faces, 3}, opts.dtype(at::kInt));
+    a.vertices_out = fptr_mut(vo);
+    a.faces_out = info.num_faces > 0 ? fo.data_ptr<int32_t>() : nullptr;
+    return {vo, fo};
+  }
+};
+
+float mcl_key_float(uint32_t k) {       // gridscan.h::hgs_key_float on the host
+  const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+}  // namespace
+
+// (labels [V] int32, comp_faces [V] int32, comp_diag2 [V] fp32, rounds, faces with an index out of range)
+std::tuple<Tensor, Tensor, Tensor, int64_t, int64_t> meshclean_components(const Tensor& vertices, const Tensor& faces) {
+  at::NoGradGuard ng;
+  MclCall c(vertices, faces, "mesh_components");
+  const auto rb = c.components();
+  return {c.labels, c.comp_faces, c.comp_diag2, rb.first, rb.second};
+}
+
+// (vertices [V', 3], faces [F', 3] int32, vertex_src [V'] int32 or undefined, rounds)
+std::tuple<Tensor, Tensor, c10::optional<Tensor>, int64_t> meshclean_clean(const Tensor& vertices, const Tensor& faces,
+                                                                             int64_t min_f, double min_d, bool want_index) {
+  at::NoGradGuard ng;
+  MclCall c(vertices, faces, "clean_mesh");
+  const auto rb = c.components();
+  c.a.min_f = (int32_t)std::min<int64_t>(std::max<int64_t>(min_f, 0), 0x7fffffffll);
+  c.a.min_d = (float)min_d;
+  check_rc(hgs_meshclean_clean_mark(&c.a, c.stream), "hgs_meshclean_clean_mark");
+  const hgs_meshclean_info info = c.read_info();
+  c.no_bad_faces(info, "clean_mesh");
+  const auto out = c.outputs(info);
+  c10::optional<Tensor> vertex_src;
+  if (want_index) {
+    vertex_src = at::empty({(int64_t)info.num_vertices}, at::TensorOptions().device(c.dev).dtype(at::kInt));
+    c.a.vertex_src = info.num_vertices > 0 ? vertex_src->data_ptr<int32_t>() : nullptr;
+  }
+  check_rc(hgs_meshclean_clean_emit(&c.a, &info, c.stream), "hgs_meshclean_clean_emit");
+  return {out.first, out.second, vertex_src, rb.first};
+}
+
+// (vertices [V', 3], faces [F', 3] int32, g, cell edge, bisection launches): the caller has ruled out the no-op cases
+std::tuple<Tensor, Tensor, int64_t, double, int64_t> meshclean_decimate(const Tensor& vertices, const Tensor& faces,
+                                                                        int64_t target) {
+  at::NoGradGuard ng;
+  MclCall c(vertices, faces, "decimate_mesh");
+  if (target < 0) throw std::runtime_error("decimate_mesh: the face budget must not be negative");
+  check_rc(hgs_meshclean_begin(&c.a, c.stream), "hgs_meshclean_begin");
+  Tensor counts_dev = at::empty({3}, at::TensorOptions().device(c.dev).dtype(at::kInt));
+  auto* counts_ptr = reinterpret_cast<uint32_t*>(counts_dev.data_ptr());
+  // the header's bisection, two steps per launch: mid and the two mids that can follow it
+  int32_t lo = 1, hi = HGS_MESHCLEAN_G_MAX + 1;
+  int64_t launches = 0;
+  while (hi - lo > 1) {
+    if (launches >= 10) throw std::runtime_error("decimate_mesh: the bisection did not end in 10 launches");
+    const int32_t mid = (lo + hi) / 2, below = (lo + mid) / 2, above = (mid + hi) / 2;
+    const int32_t g[3] = {mid, mid - lo > 1 ? below : 0, hi - mid > 1 ? above : 0};
+    if (hipMemsetAsync(counts_ptr, 0, 12, c.stream) != hipSuccess) throw std::runtime_error("decimate_mesh: hipMemsetAsync failed");
+    check_rc(hgs_meshclean_count(&c.a, g, counts_ptr, c.stream), "hgs_meshclean_count");
+    uint32_t counts[3];
+    c.read(counts, counts_ptr, sizeof(counts), "the surviving-face counts");
+    ++launches;
+    if ((int64_t)counts[0] <= target) {
+      lo = mid;
+      if (g[2] > 0) { if ((int64_t)counts[2] <= target) lo = above; else hi = above; }
+    } else {
+      hi = mid;
+      if (g[1] > 0) { if ((int64_t)counts[1] <= target) lo = below; else hi = below; }
+    }
+  }
+  check_rc(hgs_meshclean_decimate_mark(&c.a, lo, c.stream), "hgs_meshclean_decimate_mark");
+  const hgs_meshclean_info info = c.read_info();
+  c.no_bad_faces(info, "decimate_mesh");
+  const auto out = c.outputs(info);
+  check_rc(hgs_meshclean_decimate_emit(&c.a, &info, c.stream), "hgs_meshclean_decimate_emit");
+  float emax = 0.0f;
+  for (int k = 0; k < 3; ++k) emax = std::max(emax, mcl_key_float(info.bmax[k]) - mcl_key_float(info.bmin[k]));
+  return {out.first, out.second, (int64_t)lo, (double)(emax / (float)lo), launches};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torch binding of libhgs_rast.so (include/hgs_rast.h): autograd node, capacity logic, the one host wait";
   m.def("rasterize", &rasterize, py::call_guard<py::gil_scoped_release>());
@@ -1720,6 +1888,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("attr") = py::none(), py::arg("shade_normals") = false, py::arg("background") = 0.0,
         py::arg("want_rast") = false, py::call_guard<py::gil_scoped_release>());
   m.def("meshview_interpolate", &meshview_interpolate, py::arg("attr"), py::arg("rast"), py::arg("faces"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("meshclean_components", &meshclean_components, py::arg("vertices"), py::arg("faces"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("meshclean_clean", &meshclean_clean, py::arg("vertices"), py::arg("faces"), py::arg("min_f"), py::arg("min_d"),
+        py::arg("want_index") = false, py::call_guard<py::gil_scoped_release>());
+  m.def("meshclean_decimate", &meshclean_decimate, py::arg("vertices"), py::arg("faces"), py::arg("target"),
         py::call_guard<py::gil_scoped_release>());
   m.def("set_stage_events", &set_stage_events);
   m.def("device_state", &device_state);

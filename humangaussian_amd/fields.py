@@ -7,7 +7,8 @@ the opacity cut, the normalisation, the per-block cut of the sum, the inside rul
 The field is bit-reproducible from call to call.  `GaussianField` keeps a field's plan and lists and evaluates it at
 arbitrary points (`hgs_fsample`: density, outward normal, opacity-weighted colour) - the vertex attributes of
 `extract_mesh_attributes`, an extension the reference has no counterpart for.  No CPU path: CPU tensors raise.  The reference's `clean_mesh` /
-`decimate_mesh` (kiui + pymeshlab, CPU) are not part of this module."""
+`decimate_mesh` (kiui + pymeshlab, CPU) are not reproduced; `extract_clean_mesh(clean=True, decimate_target=...)` finishes the
+mesh on the device with meshclean.py's component filter and vertex clustering instead."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -15,6 +16,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .meshclean import MIN_D, MIN_F, clean_mesh, decimate_mesh
 
 OPACITY_CUT = 0.005
 
@@ -169,9 +171,18 @@ def gaussian_colors(model) -> torch.Tensor:
     return torch.clamp_min(SH_C0 * model._features_dc.detach()[:, 0] + 0.5, 0.0)
 
 
+def _finish_mesh(vertices, triangles, clean, decimate_target, min_f, min_d):
+    """the reference's order: clean_mesh, then decimate_mesh when there are more triangles than the target"""
+    if clean:
+        vertices, triangles = clean_mesh(vertices, triangles, min_f=min_f, min_d=min_d)
+    if decimate_target > 0 and triangles.shape[0] > decimate_target:
+        vertices, triangles = decimate_mesh(vertices, triangles, decimate_target)
+    return vertices, triangles
+
+
 def extract_mesh(model, density_thresh: float = 1, resolution: int = 128) -> Tuple[torch.Tensor, torch.Tensor]:
     """(vertices (V,3) fp32 in world space, faces (T,3) int32) of the avatar's density iso-surface: the reference's
-    extract_mesh up to (not including) clean_mesh / decimate_mesh."""
+    extract_mesh up to (not including) clean_mesh / decimate_mesh.  `extract_clean_mesh` goes on from there."""
     if isinstance(model, (tuple, list)):
         occ, center, scale = extract_fields(model, resolution)
     else:
@@ -183,12 +194,24 @@ def extract_mesh(model, density_thresh: float = 1, resolution: int = 128) -> Tup
     return vertices, triangles
 
 
+def extract_clean_mesh(model, density_thresh: float = 1, resolution: int = 128, clean: bool = True, decimate_target: int = 0,
+                       min_f: int = MIN_F, min_d: float = MIN_D) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's extract_mesh to its end, on the device: `extract_mesh`, then - in world space, in the reference's
+    order - clean=True removes floaters, degenerate faces and unreferenced vertices (`meshclean.clean_mesh` with min_f,
+    min_d) and decimate_target > 0 decimates to at most that many faces when the mesh has more
+    (`meshclean.decimate_mesh`; the reference's decimate_target default is 1e5).  Not pymeshlab's algorithms
+    (INTEGRATION.md 13).  clean=False, decimate_target=0 returns `extract_mesh`'s result, bit for bit."""
+    vertices, triangles = extract_mesh(model, density_thresh, resolution)
+    return _finish_mesh(vertices, triangles, clean, decimate_target, min_f, min_d)
+
+
 def extract_mesh_attributes(model, density_thresh: float = 1, resolution: int = 128, colors: Optional[torch.Tensor] = None):
     """`extract_mesh` with vertex attributes (an extension; the reference stops at vertices and faces):
     (vertices, faces, normals (V,3), colors (V,3) or None).  vertices and faces are those of `extract_mesh`, bit for bit;
     normals and colors are the field's outward unit normal and opacity-weighted colour at every vertex
     (`GaussianField.sample` at the vertices' normalised coordinates, before they go to world space).  The Gaussians'
-    colours are `colors` (P,3) if given; else `gaussian_colors(model)` for a model, and None for the four-tensor form."""
+    colours are `colors` (P,3) if given; else `gaussian_colors(model)` for a model, and None for the four-tensor form.
+    The raw iso-surface only: `extract_clean_mesh_attributes` is the same call for the cleaned, decimated mesh."""
     field = GaussianField(model, resolution)
     if colors is None and not isinstance(model, (tuple, list)):
         colors = gaussian_colors(model)
@@ -196,4 +219,23 @@ def extract_mesh_attributes(model, density_thresh: float = 1, resolution: int = 
     vertices = vertices / (resolution - 1.0) * 2 - 1
     _, normals, vertex_colors = field.sample(vertices, colors, normalized=True)
     vertices = vertices / field.scale + field.center
+    return vertices, triangles, normals, vertex_colors
+
+
+def extract_clean_mesh_attributes(model, density_thresh: float = 1, resolution: int = 128, colors: Optional[torch.Tensor] = None,
+                                  clean: bool = True, decimate_target: int = 0, min_f: int = MIN_F, min_d: float = MIN_D):
+    """`extract_mesh_attributes` for the finished mesh: (vertices, faces, normals, colors or None) with vertices and faces
+    those of `extract_clean_mesh(model, density_thresh, resolution, clean, decimate_target, min_f, min_d)`, bit for bit, and the
+    normals and colours sampled at the FINAL vertices (`GaussianField.sample` in world coordinates, normalized=False) -
+    a decimated vertex is a cell mean and lies beside the iso-surface, so its attributes are the field's there.  One
+    field build serves the surface and the samples.  With clean=False and decimate_target=0 the mesh is the raw
+    iso-surface (attributes sampled at its world-space vertices)."""
+    field = GaussianField(model, resolution)
+    if colors is None and not isinstance(model, (tuple, list)):
+        colors = gaussian_colors(model)
+    vertices, triangles = marching_cubes(field.occ, density_thresh)
+    vertices = vertices / (resolution - 1.0) * 2 - 1
+    vertices = vertices / field.scale + field.center
+    vertices, triangles = _finish_mesh(vertices, triangles, clean, decimate_target, min_f, min_d)
+    _, normals, vertex_colors = field.sample(vertices, colors, normalized=False)
     return vertices, triangles, normals, vertex_colors

@@ -946,6 +946,97 @@ size_t hgs_meshview_list_bytes(const hgs_meshview_info* info_host);
 int hgs_meshview_draw(const hgs_meshview_args* args, const hgs_meshview_info* info_host, void* stream);
 int hgs_meshview_interpolate(const hgs_meshview_args* args, void* stream);
 
+/* ---- mesh cleaning and decimation (what follows marching cubes in the reference's extract_mesh) -------------------------
+ * The reference (gs_renderer.py:333-361) calls kiui's clean_mesh and decimate_mesh, pymeshlab on the CPU.  pymeshlab's
+ * isotropic remeshing, quadric edge collapse and non-manifold repair are NOT reproduced: floaters are removed by connected
+ * components, the mesh is decimated by vertex clustering on a uniform grid.  This definition is the contract
+ * (tests/mesh_clean_reference.py restates it in numpy); every result is independent of the order in which threads arrive
+ * and the same from call to call.  vertices [V][3] fp32, faces [F][3] int32.
+ *
+ * A face with an index outside [0, V) is IGNORED everywhere below (it connects nothing, is counted nowhere, is never kept)
+ * and counted in info->bad_faces.  A vertex with a coordinate that is not finite contributes to no box; in the clustering
+ * grid and on the lattice it is clamped as hgs_grid_cell1 clamps (NaN -> 0).
+ *
+ * a. COMPONENTS.  Vertices are connected through the faces that share them (a face with a repeated index connects its
+ *    vertices like any other).  labels[v] = the smallest vertex index of v's component; a vertex no face references is a
+ *    component of its own.  Per component, at index L = its label (all other entries 0):
+ *      comp_faces[L] = the number of its faces;
+ *      comp_diag2[L] = (dx dx + dy dy) + dz dz in fp32, d = fp32(max - min) of its finite vertices per axis (integer atomics
+ *                      on ordered float keys); 0 for a component without a finite vertex.
+ *    Built as ROUNDS of launches: per face m = min of its three labels goes by atomicMin into the three labels and into
+ *    the labels' own labels (the roots are hooked); then one pointer-jumping pass labels[v] = labels[labels[v]].  Labels
+ *    only decrease; changed[r] (DEVICE) counts the waves that lowered a label in round r, and the labels are final after a
+ *    round with changed[r] == 0.  The caller reads `changed` (every few rounds) and stops there; V + 1 rounds always suffice.
+ * b. CLEAN.  D2 = the squared diagonal, computed as comp_diag2 is, of the box of ALL finite vertices.  p = min_d / 100.0f,
+ *    thr = (p * p) * D2, all fp32.  A face is KEPT iff its three indices are distinct (and in range), comp_faces[L] >= min_f
+ *    and NOT comp_diag2[L] < thr, L = the label of its vertices.  A vertex is kept iff a kept face references it.  Output:
+ *    the kept vertices in ascending original index (vertex_src [V'] = their original indices, optional), the kept faces in
+ *    original order, re-indexed.
+ * c. DECIMATE by vertex clustering.  Box: lo = min, ext = fp32(max - min) per axis of the finite vertices, emax = the
+ *    longest ext.  Grid of g cells per axis, 1 <= g <= HGS_MESHCLEAN_G_MAX: inv_h = (float)g / emax, the cell of a vertex =
+ *    hgs_grid_cell1(x, lo, inv_h, g) per axis, its key (cz g + cy) g + cx (30 bits); the cell edge h = emax / (float)g is
+ *    only reported.  surviving(g) = the faces whose three vertices lie in three different cells; hgs_meshclean_count adds
+ *    surviving(g[k]) to counts[k] (DEVICE, zeroed by the caller) for up to three grids in one launch (g[k] < 1: skipped).
+ *    CHOOSING g is the caller's bisection and nothing else: lo = 1, hi = G_MAX + 1; while hi - lo > 1: mid = (lo + hi) / 2,
+ *    lo = mid if surviving(mid) <= target else hi = mid; g = lo.  surviving(1) = 0, so surviving(g) <= target always,
+ *    although surviving is not monotone.  (mid, (lo + mid) / 2 and (mid + hi) / 2 in one launch are two steps of it.)
+ *    NEW VERTICES: one per cell that a surviving face references, ordered by the smallest vertex index in the cell.  Its
+ *    position is the mean of ALL input vertices in the cell on a lattice: per axis q = fminf(fmaxf(floorf((x - lo) * qs +
+ *    0.5f), 0), 1048576) with qs = 1048576.0f / emax (fp32), summed in 64-bit integers (atomics) with the count n; then in
+ *    fp64 m = (double)sum / (double)n and position = (float)((double)lo + m * ((double)emax / 1048576.0)).  No float atomics.
+ *    NEW FACES: the surviving faces in original order, indices replaced by their cells' new vertices, orientation kept.
+ *    Faces with the same three new vertices in any order or orientation are duplicates: the lowest original index stays.
+ *    Both equivalence classes (cell -> lowest vertex, vertex set -> lowest face) are hash tables of a power-of-two capacity of
+ *    at least twice the items, built by atomicCAS / atomicMin whose RETURNED values alone are used, looked up in a later
+ *    launch, every probe loop bounded by the capacity; running into the bound sets info->error (the result is then void).
+ * Calls (no call allocates or waits; `scratch` = hgs_meshclean_scratch_bytes(V, F) bytes, shared by all of them; `info`
+ * DEVICE, 64 bytes, rewritten by each _begin):
+ *   components: hgs_meshclean_begin (labels = identity, box, bad_faces) -> hgs_meshclean_rounds (n rounds, changed [n]
+ *     DEVICE) until a round changed nothing -> hgs_meshclean_components (comp_faces, comp_diag2).
+ *   clean: the components, then hgs_meshclean_clean_mark (the keep rule and the two compactions; info->num_vertices /
+ *     num_faces) -> the caller copies *info to the host and allocates -> hgs_meshclean_clean_emit.
+ *   decimate: hgs_meshclean_begin with labels == NULL -> hgs_meshclean_count per bisection launch -> hgs_meshclean_decimate_mark
+ *     (g) -> copy *info, allocate -> hgs_meshclean_decimate_emit.
+ * Limits: 0 <= V, F <= 2^29 (hgs_meshclean_scratch_bytes returns 0 beyond, the calls HGS_EINVAL).  V == 0 or F == 0 where
+ * nothing is to do: HGS_OK without a launch.  HGS_EINVAL before any launch for args == NULL, sizes outside the limits, a
+ * NULL pointer of an array the call uses, g outside [1, G_MAX], an info_host that holds an error, bad faces or counts
+ * above V / F.  v17 gained these exports without a change of any earlier signature. */
+#define HGS_MESHCLEAN_G_MAX 1024
+#define HGS_MESHCLEAN_MAX_ITEMS (1 << 29)
+#define HGS_MESHCLEAN_ERR_CELL_TABLE 1u   /* info->error bits: a probe loop ran into its bound */
+#define HGS_MESHCLEAN_ERR_FACE_TABLE 2u
+typedef struct hgs_meshclean_info {
+  uint32_t bmin[3], bmax[3];        /* ordered-key images of the box of the finite vertices */
+  uint32_t bad_faces;               /* faces with an index outside [0, V) */
+  uint32_t error;                   /* HGS_MESHCLEAN_ERR_* */
+  uint32_t num_vertices, num_faces; /* of the output (clean_mark, decimate_mark) */
+  uint32_t reserved[6];
+} hgs_meshclean_info;
+typedef struct hgs_meshclean_args {
+  int32_t V, F;
+  const float* vertices;
+  const int32_t* faces;
+  void* scratch;
+  hgs_meshclean_info* info;         /* DEVICE */
+  int32_t* labels;                  /* [V] */
+  int32_t* comp_faces;              /* [V] */
+  float* comp_diag2;                /* [V] */
+  int32_t min_f;                    /* clean_mark */
+  float min_d;
+  float* vertices_out;              /* emit: [info_host->num_vertices][3] */
+  int32_t* faces_out;               /* emit: [info_host->num_faces][3] */
+  int32_t* vertex_src;              /* clean_emit: [num_vertices], may be NULL */
+} hgs_meshclean_args;
+size_t hgs_meshclean_scratch_bytes(int32_t V, int32_t F);   /* 0 for sizes the calls refuse; grows with V and with F */
+int hgs_meshclean_begin(const hgs_meshclean_args* args, void* stream);
+int hgs_meshclean_rounds(const hgs_meshclean_args* args, int32_t rounds, uint32_t* changed, void* stream);
+int hgs_meshclean_components(const hgs_meshclean_args* args, void* stream);
+int hgs_meshclean_clean_mark(const hgs_meshclean_args* args, void* stream);
+int hgs_meshclean_clean_emit(const hgs_meshclean_args* args, const hgs_meshclean_info* info_host, void* stream);
+int hgs_meshclean_count(const hgs_meshclean_args* args, const int32_t* g, uint32_t* counts, void* stream);
+int hgs_meshclean_decimate_mark(const hgs_meshclean_args* args, int32_t g, void* stream);
+int hgs_meshclean_decimate_emit(const hgs_meshclean_args* args, const hgs_meshclean_info* info_host, void* stream);
+
 /* Library / ABI version (bumped on any signature change). */
 int hgs_abi_version(void);
 
