@@ -7,6 +7,7 @@ Only what the rasterize hot path needs:
   renderer.py      render() / Renderer.render() mirrors (the reference's two call sites)
   view_parallel.py view-parallel multi-GPU rendering (one RCCL all-gather per step)
   step_images.py   guidance_images(): the guidance's two images and the opacity losses of a step
+  photometric.py   photometric_loss(): L1 + D-SSIM and PSNR of image fitting; l1_loss / ssim / psnr drop-ins
   surface.py       SurfaceSampler / create_from_pcd: the body surface sampled and the initial Gaussians built on the device
   mesh_view.py     MeshView: the body mesh rasterized forward-only (the animation loop's mesh mode, mesh previews)
   meshclean.py     mesh_components / clean_mesh / decimate_mesh: the extracted mesh without floaters, decimated to a face budget
@@ -20,6 +21,7 @@ from .rasterizer import (  # noqa: F401
 )
 
 from .meshclean import clean_mesh, decimate_mesh, mesh_components  # noqa: F401
+from .photometric import PhotometricLoss, photometric_loss  # noqa: F401
 from .step_images import StepImages, guidance_images  # noqa: F401
 from .surface import (  # noqa: F401
     SurfaceSampler,
@@ -30,5 +32,5 @@ from .surface import (  # noqa: F401
 )
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
-           "rasterize_gaussians_batch", "StepImages", "guidance_images", "SurfaceSampler", "sample_surface",
+           "rasterize_gaussians_batch", "StepImages", "guidance_images", "PhotometricLoss", "photometric_loss", "SurfaceSampler", "sample_surface",
            "create_from_points", "create_from_pcd", "init_from_body", "mesh_components", "clean_mesh", "decimate_mesh"]

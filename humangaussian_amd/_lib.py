@@ -104,6 +104,23 @@ class HgsStepImagesArgs(Structure):
     ]
 
 
+PM_TILE_H, PM_TILE_W, PM_FINISH_CHUNK = 32, 32, 64
+PM_WINDOW = (0.00102838012, 0.00759875821, 0.0360007733, 0.109360687, 0.213005528, 0.266011715,
+             0.213005528, 0.109360687, 0.0360007733, 0.00759875821, 0.00102838012)     # HGS_PM_WINDOW, to be read as fp32
+
+
+class HgsPhotometricArgs(Structure):
+    """ctypes mirror of `hgs_photometric_args` (hgs_photometric_forward / _backward)."""
+    _fields_ = [
+        ("B", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("with_grad", c_int32), ("psnr_per_plane", c_int32),
+        ("weight_l1", c_float), ("weight_dssim", c_float),
+        ("image", c_void_p), ("gt", c_void_p), ("workspace", c_void_p),
+        ("loss", c_void_p), ("l1", c_void_p), ("ssim", c_void_p), ("ssim_image", c_void_p), ("sqerr", c_void_p), ("psnr", c_void_p),
+        ("grad_loss", c_void_p), ("grad_l1", c_void_p), ("grad_ssim", c_void_p), ("grad_ssim_image", c_void_p),
+        ("grad_image", c_void_p),
+    ]
+
+
 class HgsFsampleArgs(Structure):
     """ctypes mirror of `hgs_fsample_args` (hgs_fsample)."""
     _fields_ = [
@@ -235,6 +252,9 @@ EXPORTS = {
     "hgs_step_images_workspace_bytes": (c_size_t, [c_int32] * 5),
     "hgs_step_images_forward": (ctypes.c_int, [POINTER(HgsStepImagesArgs), c_void_p]),
     "hgs_step_images_backward": (ctypes.c_int, [POINTER(HgsStepImagesArgs), c_void_p]),
+    "hgs_photometric_workspace_bytes": (c_size_t, [c_int32] * 5),
+    "hgs_photometric_forward": (ctypes.c_int, [POINTER(HgsPhotometricArgs), c_void_p]),
+    "hgs_photometric_backward": (ctypes.c_int, [POINTER(HgsPhotometricArgs), c_void_p]),
     "hgs_mesh_grid_plan": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "hgs_mesh_grid_bytes": (c_size_t, [c_void_p]),
     "hgs_mesh_grid_build": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

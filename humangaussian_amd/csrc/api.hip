@@ -30,6 +30,7 @@ __device__ unsigned long long hgs_tl[HGS_TL_KERNELS][HGS_TL_SLOTS][4];
 #include "lbs.hip"
 #include "pose.hip"
 #include "step_images.hip"
+#include "photometric.hip"
 #include "surface.hip"
 #include "meshview.hip"
 #include "meshclean.hip"
@@ -1142,6 +1143,50 @@ int hgs_step_images_backward(const hgs_step_images_args* args, void* stream_) {
     HGS_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(hgs_k_si_bwd_write, dim3((unsigned)blocks), dim3(HGS_SI_THREADS), 0, stream, a, P, (int)per_plane, planes);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+namespace {
+// sizes both entry points and the workspace rule accept
+bool photometric_sizes_ok(int32_t B, int32_t C, int32_t H, int32_t W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1 || H > HGS_SI_MAX_DIM || W > HGS_SI_MAX_DIM) return false;
+  if ((long long)B * C > 65535) return false;
+  return (long long)B * C * H * W <= 0x7fffffffll;
+}
+}  // namespace
+
+size_t hgs_photometric_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t with_grad) {
+  if (!photometric_sizes_ok(B, C, H, W)) return 0;
+  return pm_carve(B, C, H, W, with_grad).total;
+}
+
+// Two launches (photometric.hip): one workgroup per tile of a plane, then one workgroup that adds the partials.
+int hgs_photometric_forward(const hgs_photometric_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_photometric_args& a = *args;
+  if (!photometric_sizes_ok(a.B, a.C, a.H, a.W)) return HGS_EINVAL;
+  if (!a.image || !a.gt || !a.workspace || !a.loss || !a.l1 || !a.ssim || !a.ssim_image || !a.sqerr || !a.psnr) return HGS_EINVAL;
+  const int tiles = pm_tiles(a.H, a.W);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_pm_forward, dim3((unsigned)tiles, (unsigned)(a.B * a.C)), dim3(HGS_PM_THREADS), 0, stream, a,
+                     pm_tiles_x(a.W));
+  HGS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hgs_k_pm_finish, dim3(1), dim3(HGS_PM_FINISH_THREADS), 0, stream, a, tiles);
+  HGS_LAUNCH_CHECK();
+  return HGS_OK;
+}
+
+// One launch: the three derivative maps of the forward filtered, and the sign term.
+int hgs_photometric_backward(const hgs_photometric_args* args, void* stream_) {
+  if (!args) return HGS_EINVAL;
+  const hgs_photometric_args& a = *args;
+  if (!photometric_sizes_ok(a.B, a.C, a.H, a.W)) return HGS_EINVAL;
+  if (!a.grad_loss && !a.grad_l1 && !a.grad_ssim && !a.grad_ssim_image) return HGS_OK;
+  if (!a.image || !a.gt || !a.workspace || !a.grad_image) return HGS_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(hgs_k_pm_backward, dim3((unsigned)pm_tiles(a.H, a.W), (unsigned)(a.B * a.C)), dim3(HGS_PM_THREADS), 0, stream, a,
+                     pm_tiles_x(a.W));
   HGS_LAUNCH_CHECK();
   return HGS_OK;
 }

@@ -1158,6 +1158,85 @@ std::tuple<c10::optional<Tensor>, c10::optional<Tensor>> step_images_backward(
   return {a.grad_rgb ? c10::optional<Tensor>(d_render) : c10::nullopt, want_depth ? c10::optional<Tensor>(d_depth) : c10::nullopt};
 }
 
+// ---- the photometric loss (include/hgs_rast.h: hgs_photometric_*): two launches forward and one backward on the current
+// stream, the workspace from the caching allocator, nothing read back.  image and gt (B, C, H, W) fp32 contiguous.  Forward
+// returns (loss, l1, ssim (0-dim), ssim_image (B,), sqerr (B, C), psnr (B,) or (B C,), workspace); with_grad = false leaves
+// the derivative maps out of the workspace, which then cannot be handed to the backward.
+namespace {
+hgs_photometric_args pm_args(const Tensor& image, const Tensor& gt, double weight_l1, double weight_dssim, const char* who) {
+  if (image.dim() != 4 || gt.sizes() != image.sizes()) throw std::runtime_error(std::string(who) + ": image and gt must be (B, C, H, W) of one shape");
+  const int64_t B = image.size(0), C = image.size(1), H = image.size(2), W = image.size(3);
+  if (B < 1 || C < 1 || H < 1 || W < 1 || H > HGS_SI_MAX_DIM || W > HGS_SI_MAX_DIM || B * C > 65535 || B * C * H * W > 0x7fffffffll)
+    throw std::runtime_error(std::string(who) + ": 1..65535 planes of 1.." + std::to_string(HGS_SI_MAX_DIM) + " pixels a side, fewer than 2^31 elements in all");
+  hgs_photometric_args a{};
+  a.B = (int32_t)B; a.C = (int32_t)C; a.H = (int32_t)H; a.W = (int32_t)W;
+  a.weight_l1 = (float)weight_l1;
+  a.weight_dssim = (float)weight_dssim;
+  a.image = image.data_ptr<float>();
+  a.gt = gt.data_ptr<float>();
+  return a;
+}
+}  // namespace
+
+std::vector<Tensor> photometric_forward(const Tensor& image, const Tensor& gt, double weight_l1, double weight_dssim,
+                                        bool psnr_per_plane, bool with_grad) {
+  at::NoGradGuard ng;
+  const c10::Device dev = image.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(image, dev, at::kFloat, "photometric_forward: image");
+  need_dev(gt, dev, at::kFloat, "photometric_forward: gt");
+  hgs_photometric_args a = pm_args(image, gt, weight_l1, weight_dssim, "photometric_forward");
+  a.with_grad = with_grad ? 1 : 0;
+  a.psnr_per_plane = psnr_per_plane ? 1 : 0;
+  const auto fopt = image.options();
+  Tensor loss = at::empty({}, fopt), l1 = at::empty({}, fopt), ssim = at::empty({}, fopt), ssim_image = at::empty({a.B}, fopt);
+  Tensor sqerr = at::empty({a.B, a.C}, fopt), psnr = at::empty({psnr_per_plane ? (int64_t)a.B * a.C : (int64_t)a.B}, fopt);
+  Tensor work = at::empty({(int64_t)hgs_photometric_workspace_bytes(a.B, a.C, a.H, a.W, a.with_grad)}, fopt.dtype(at::kByte));
+  a.workspace = work.data_ptr();
+  a.loss = loss.data_ptr<float>();
+  a.l1 = l1.data_ptr<float>();
+  a.ssim = ssim.data_ptr<float>();
+  a.ssim_image = ssim_image.data_ptr<float>();
+  a.sqerr = sqerr.data_ptr<float>();
+  a.psnr = psnr.data_ptr<float>();
+  check_rc(hgs_photometric_forward(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_photometric_forward");
+  return {loss, l1, ssim, ssim_image, sqerr, psnr, work};
+}
+
+// The gradient with respect to image.  The forward's workspace (with_grad = true); the four incoming gradients, each
+// optional (None: absent).  Returns None when all four are absent.
+c10::optional<Tensor> photometric_backward(const Tensor& image, const Tensor& gt, const Tensor& workspace, double weight_l1,
+                                           double weight_dssim, c10::optional<Tensor> grad_loss, c10::optional<Tensor> grad_l1,
+                                           c10::optional<Tensor> grad_ssim, c10::optional<Tensor> grad_ssim_image) {
+  at::NoGradGuard ng;
+  const c10::Device dev = image.device();
+  if (!dev.is_cuda()) throw std::runtime_error("humangaussian_amd: tensors must live on a HIP device");
+  DeviceSwitch guard(dev.index());
+  need_dev(image, dev, at::kFloat, "photometric_backward: image");
+  need_dev(gt, dev, at::kFloat, "photometric_backward: gt");
+  need_dev(workspace, dev, at::kByte, "photometric_backward: workspace");
+  hgs_photometric_args a = pm_args(image, gt, weight_l1, weight_dssim, "photometric_backward");
+  if (workspace.numel() != (int64_t)hgs_photometric_workspace_bytes(a.B, a.C, a.H, a.W, 1))
+    throw std::runtime_error("photometric_backward: the workspace must be that of a forward with with_grad = true");
+  auto grad = [&](c10::optional<Tensor>& g, int64_t n, const char* name) -> const float* {
+    if (!g.has_value() || !g->defined()) return nullptr;
+    need_dev(*g, dev, at::kFloat, name);
+    if (g->numel() != n) throw std::runtime_error(std::string(name) + " has " + std::to_string(g->numel()) + " elements, expected " + std::to_string(n));
+    return g->data_ptr<float>();
+  };
+  a.grad_loss = grad(grad_loss, 1, "photometric_backward: grad_loss");
+  a.grad_l1 = grad(grad_l1, 1, "photometric_backward: grad_l1");
+  a.grad_ssim = grad(grad_ssim, 1, "photometric_backward: grad_ssim");
+  a.grad_ssim_image = grad(grad_ssim_image, a.B, "photometric_backward: grad_ssim_image");
+  if (!a.grad_loss && !a.grad_l1 && !a.grad_ssim && !a.grad_ssim_image) return c10::nullopt;
+  Tensor d_image = at::empty_like(image);
+  a.workspace = workspace.data_ptr();
+  a.grad_image = d_image.data_ptr<float>();
+  check_rc(hgs_photometric_backward(&a, c10::hip::getCurrentHIPStream(dev.index()).stream()), "hgs_photometric_backward");
+  return d_image;
+}
+
 void set_stage_events(const c10::optional<std::vector<int64_t>>& fwd, const c10::optional<std::vector<int64_t>>& bwd) {
   g_stage_fwd.clear();
   g_stage_bwd.clear();
@@ -1865,7 +1944,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("depth_global_max"), py::arg("tie_counts"), py::arg("h"), py::arg("w"), py::arg("half_images"),
         py::arg("grad_rgb") = py::none(), py::arg("grad_depth") = py::none(), py::arg("grad_loss_sparsity") = py::none(),
         py::arg("grad_loss_opaque") = py::none(), py::call_guard<py::gil_scoped_release>());
-  m.def("mesh_build", &mesh_build, py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
+  m.def("photometric_forward", &photometric_forward, py::arg("image"), py::arg("gt"), py::arg("weight_l1"),
+        py::arg("weight_dssim"), py::arg("psnr_per_plane") = false, py::arg("with_grad") = true,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("photometric_backward", &photometric_backward, py::arg("image"), py::arg("gt"), py::arg("workspace"),
+        py::arg("weight_l1"), py::arg("weight_dssim"), py::arg("grad_loss") = py::none(), py::arg("grad_l1") = py::none(),
+        py::arg("grad_ssim") = py::none(), py::arg("grad_ssim_image") = py::none(), py::call_guard<py::gil_scoped_release>());
+  m.def("mesh_build", &mesh_build,py::arg("vertices"), py::arg("faces"), py::call_guard<py::gil_scoped_release>());
   m.def("mesh_query", &mesh_query, py::arg("points"), py::arg("vertices"), py::arg("faces"), py::arg("grid") = py::none(),
         py::arg("raystab") = false, py::arg("want_uvw") = true, py::call_guard<py::gil_scoped_release>());
   m.def("field_extract", &field_extract, py::arg("xyz"), py::arg("opacity"), py::arg("scaling"), py::arg("rotation"),

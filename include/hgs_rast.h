@@ -627,6 +627,72 @@ size_t hgs_step_images_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t 
 int hgs_step_images_forward(const hgs_step_images_args* args, void* stream);
 int hgs_step_images_backward(const hgs_step_images_args* args, void* stream);
 
+/* ---- the photometric loss of image fitting: L1 + D-SSIM forward and backward, PSNR ----------------------------------------
+ * The reference's second training loop (gaussiansplatting/train.py) scores a render against a photograph with
+ *   loss = (1 - lambda) l1_loss(image, gt) + lambda (1 - ssim(image, gt))         (utils/loss_utils.py, lambda_dssim = 0.2)
+ * and evaluates with the same two functions and psnr (utils/image_utils.py).  hgs_photometric_forward computes all of them
+ * in two launches, hgs_photometric_backward the gradient with respect to `image` in one; nothing is read back.
+ * Inputs: image (x below) and gt (y), both [B][C][H][W] fp32, contiguous, finite.  N = B C H W.
+ * Definition, every operation in fp32 rounded once (the library is built with -ffp-contract=off) unless said otherwise:
+ *   w[11] = HGS_PM_WINDOW: exp(-(i - 5)^2 / (2 1.5^2)) normalised to sum 1, the fp32 values the reference's gaussian()
+ *           holds.  F(v)(p) = sum_j w[j] (sum_i w[i] v(p + (j - 5, i - 5))): rows first, then columns, taps added in ascending
+ *           order from 0, v = 0 outside the plane (conv2d's zero padding of 5).  The reference multiplies by the 121
+ *           products w[j] w[i] instead; the two differ by fp32 rounding only.
+ *   mu1 = F(x), mu2 = F(y), s1 = F(x x) - mu1 mu1, s2 = F(y y) - mu2 mu2, s12 = F(x y) - mu1 mu2   (E[x^2] - mu^2, as _ssim has it)
+ *   A1 = 2 mu1 mu2 + C1, A2 = 2 s12 + C2, B1 = mu1 mu1 + mu2 mu2 + C1, B2 = s1 + s2 + C2,  C1 = 0.01^2, C2 = 0.03^2
+ *   S = (A1 A2) / (B1 B2)                                       the SSIM map; it is not written out
+ *   ssim_image[b] = mean of S over image b,  ssim = mean of S over everything,  l1 = mean |x - y|,
+ *   sqerr[b C + c] = sum of (x - y)^2 over plane (b, c),  loss = weight_l1 l1 + weight_dssim (1.0f - ssim)
+ *   psnr[r] = 20 log10(1 / sqrt(mse[r])), mse the fp32 mean of (x - y)^2 over image r (psnr_per_plane == 0, [B] values: the
+ *           reference's view(shape[0], -1) of a 4-D input) or over plane r (psnr_per_plane != 0, [B C] values: the same
+ *           rule on a 3-D input); log10 and sqrt in fp64, rounded once; +inf where the two are identical.
+ * The sums: one workgroup per tile of HGS_PM_TILE_H x HGS_PM_TILE_W pixels of one plane adds its pixels in a fixed order in
+ * fp32 and leaves one partial per sum; one workgroup then adds a plane's partials in fp64 - lane l of a wave takes partials
+ * l, l + HGS_PM_FINISH_CHUNK, ... in order, then a fixed tree over the lanes - and the planes' sums in a fixed order.
+ * No floating-point atomics: every result is bit-reproducible and does not depend on the order the workgroups ran in.
+ * with_grad != 0: the forward also leaves three derivative maps of S in the workspace, per pixel q,
+ *   dS/ds12 = 2 A1 / (B1 B2),   dS/ds1 = -S / B2,
+ *   dS/dmu1 = 2 (mu2 (A2 - A1) + mu1 S (B1 - B2)) / (B1 B2)     (the total derivative: through s1 and s12 as well)
+ * and that workspace is an input of the backward.  with_grad == 0 (metrics only) writes none and needs no room for them.
+ * Backward: the window is symmetric, so the adjoint of the zero-padded filter is F itself:
+ *   gs = ((grad_ssim - weight_dssim grad_loss) / B + grad_ssim_image[b]) / (C H W),   gl = (grad_l1 + weight_l1 grad_loss) / N
+ *   grad_image(p) = gs (F(dS/dmu1)(p) + (2 x(p)) F(dS/ds1)(p) + y(p) F(dS/ds12)(p)) + gl sign(x(p) - y(p)),  sign(0) = 0
+ * grad_loss, grad_l1, grad_ssim (one fp32 each) and grad_ssim_image ([B]) are DEVICE memory read by the kernel; a NULL one is
+ * absent (0).  Where gs == 0 the filter is skipped (the term is 0).  gt receives no gradient.
+ * workspace: hgs_photometric_workspace_bytes(B, C, H, W, with_grad) bytes, 256-byte aligned; 0 for sizes the calls refuse.
+ * Both return HGS_EINVAL before any device work for args == NULL, B, C, H or W below 1, H or W above HGS_SI_MAX_DIM,
+ * B C > 65535, N >= 2^31, or a NULL pointer among those the call needs; the backward with all four gradients NULL: HGS_OK
+ * without a launch (grad_image is then not written).
+ * v17 gained these exports without a change of any earlier signature. */
+#define HGS_PM_TILE_H 32
+#define HGS_PM_TILE_W 32
+#define HGS_PM_FINISH_CHUNK 64
+#define HGS_PM_WINDOW {0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005528f, 0.266011715f, \
+                       0.213005528f, 0.109360687f, 0.0360007733f, 0.00759875821f, 0.00102838012f}
+typedef struct hgs_photometric_args {
+  int32_t B, C, H, W;
+  int32_t with_grad;                /* forward: write the derivative maps into the workspace */
+  int32_t psnr_per_plane;           /* psnr has B C values (the 3-D shape rule) instead of B */
+  float weight_l1, weight_dssim;    /* 1 - lambda and lambda, each rounded to fp32 by the caller */
+  const float* image;               /* [B][C][H][W] */
+  const float* gt;                  /* [B][C][H][W] */
+  void* workspace;                  /* written by the forward; with_grad: read by the backward */
+  float* loss;                      /* [1] (forward, written) */
+  float* l1;                        /* [1] */
+  float* ssim;                      /* [1] */
+  float* ssim_image;                /* [B] */
+  float* sqerr;                     /* [B C] */
+  float* psnr;                      /* [B], or [B C] with psnr_per_plane */
+  const float* grad_loss;           /* [1] on the device, or NULL (backward) */
+  const float* grad_l1;             /* [1] on the device, or NULL */
+  const float* grad_ssim;           /* [1] on the device, or NULL */
+  const float* grad_ssim_image;     /* [B] on the device, or NULL */
+  float* grad_image;                /* [B][C][H][W] (backward, every element written once) */
+} hgs_photometric_args;
+size_t hgs_photometric_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t with_grad);
+int hgs_photometric_forward(const hgs_photometric_args* args, void* stream);
+int hgs_photometric_backward(const hgs_photometric_args* args, void* stream);
+
 /* ---- closest point and signed distance to a triangle mesh (the reference's `cubvh`) ----------------------------------
  * The per-avatar anchoring of /root/reference/animation.py:333-378:
  *   BVH = cubvh.cuBVH(vertices, faces); dist, face, uvw = BVH.signed_distance(points, return_uvw=True, mode="raystab")
